@@ -9,7 +9,17 @@ neighbours' IPC-mapped ghost planes (default; --transport rccl: RCCL
 send/recv); strong scaling (the grid is fixed, each rank owns 1024/N planes).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line; the
+line's `roofline` comes from HIP events around the timed steps' own launches.
+`--full` adds the legs that take runs of their own: the CPU baselines, the
+predictor's accuracy against the oracle and, at N > 1, the parity check of
+the slab solve against the one-GPU solve (`--no-cpu-baseline`, `--no-verify`
+drop single legs of it).  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs), for output-by-output comparison of
+two builds: the inputs are seeded, the same from run to run.
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts
 the N ranks itself: a child `torch.distributed.run --nproc-per-node N` of the
@@ -23,7 +33,7 @@ of the dominant kernel -- a temporally blocked pass that fuses several sweeps
 (read phi, read rhs, write phi'), using HIP events recorded on the solve's own
 stream around its launches.  `cpu_baseline` times the NumPy restatement of the
 reference's Jacobi branch (oracle/, bit-exact to v5.py:336-346) on a bounded
-sample of the same grid, on this host, at N=1 only.
+sample of the same grid, on this host, at N=1 with --full only.
 
 `--workload cavity2d_128` is config 1: the whole projection step of the
 lid-driven cavity (128^2, Re = 100, 500 Jacobi sweeps per pressure solve) per
@@ -100,8 +110,14 @@ def parse():
     ap.add_argument("--grid", default="",
                     help="3-D workloads: override the grid as NZ,NY,NX (e.g. a small rbgs3d rehearsal)")
     ap.add_argument("--no-rhs-ws", action="store_true", help="form the RHS in-register every sweep")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the N>1 parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the timed steps: CPU baselines, the predictor's accuracy "
+                         "against the oracle, the N>1 parity check")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (at most 64 MB in all: "
+                         "a fixed, seeded sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the N>1 parity check")
     ap.add_argument("--force-slab", action="store_true",
                     help="use the RCCL slab path even on one rank (launch under torch.distributed.run)")
     ap.add_argument("--cpu-sample-planes", type=int, default=256)
@@ -127,6 +143,31 @@ def load_traffic(workload: str, n_gpus: int):
     except Exception:
         return None
     return None
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one run together (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, arrays, writers=1, suffix=""):
+    """--dump-outputs: write what the last timed step left on the device (name
+    -> tensor) as DIR/<name>.npy, float32 or float64 (integers as float64).
+    The byte budget is split evenly over the arrays (and the `writers` ranks);
+    an array past its share is written as a fixed sample of its flattened
+    elements: sorted indices from a NumPy generator with a constant seed, so
+    every run and every build samples the same cells."""
+    import torch
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (max(len(arrays), 1) * max(writers, 1))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(20240).integers(0, t.numel(), size=keep, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(d / f"{name}{suffix}.npy", t.cpu().numpy())
 
 
 def cpu_baseline(shape, iters_total_hint, gs=False):
@@ -231,6 +272,8 @@ def cavity_bench():
     nsw = ctypes.c_longlong()
     call("cfd_timing_read", ctypes.byref(ms), ctypes.byref(nsw), 1)
     call("cfd_timing_enable", 0)
+    if ARGS.dump_outputs:
+        dump_outputs(ARGS.dump_outputs, {"u": g.u, "v": g.v, "p": g.p})
     ny, nx = cfg.ny, cfg.nx
     cells = (ny - 2) * (nx - 2)
     iters = cfg.pressure_iterations
@@ -260,7 +303,7 @@ def cavity_bench():
                      "avg_launch_ms": round(launch_ms, 5)},
         "cpu_baseline": None,
     }
-    if not ARGS.no_cpu_baseline:
+    if ARGS.full and not ARGS.no_cpu_baseline:
         o = oracle.OracleCavitySolver(cfg, numpy_jacobi=True)
         n = 0
         t0 = time.perf_counter()
@@ -284,7 +327,7 @@ def predictor_bench():
     written.  value = cells / s; roofline = algorithmic bytes (20 B per f32
     cell, 40 B per f64) / the launch's HIP-event duration (the library's
     predictor timing channel).  --tau-mode exact|fast picks the SUPG tau
-    arithmetic; the CPU-baseline leg also measures the launch's relative
+    arithmetic; the CPU-baseline leg (--full) also measures the launch's relative
     L-inf against the oracle (exact arithmetic) on the sampled rows."""
     import torch
     import _pkgpath
@@ -322,6 +365,8 @@ def predictor_bench():
     nl = ctypes.c_longlong()
     call("cfd_timing_read_channel", 1, ctypes.byref(ms), ctypes.byref(nl), 1)
     call("cfd_timing_enable", 0)
+    if ARGS.dump_outputs:
+        dump_outputs(ARGS.dump_outputs, {"u_star": us, "v_star": vs, "tau": tau})
     launch_ms = ms.value / max(nl.value, 1)
     cells = ny * nx
     alg = cells * bpc
@@ -351,7 +396,7 @@ def predictor_bench():
                      "algorithmic_bytes_per_launch": alg, "avg_launch_ms": round(launch_ms, 5)},
         "cpu_baseline": None,
     }
-    if not ARGS.no_cpu_baseline:
+    if ARGS.full and not ARGS.no_cpu_baseline:
         import oracle
         rows = 512 if f64 else 1024
         hu, hv = u[:rows].cpu().numpy(), v[:rows].cpu().numpy()
@@ -581,7 +626,7 @@ def main():
             dist.barrier()
 
     verified = None
-    if use_slab and len(shape) == 3 and not ARGS.no_verify:
+    if ARGS.full and use_slab and len(shape) == 3 and not ARGS.no_verify:
         progress("verifying the slab solve against the one-GPU solve")
         verified = (verify_slabs_rbgs if gs else verify_slabs)(S, K, dist, comm, world, rank, dev)
         progress(f"verification {'bit-exact' if verified else 'MISMATCH'}")
@@ -611,6 +656,12 @@ def main():
     call("cfd_timing_read", ctypes.byref(ms), ctypes.byref(nsw), 1)
     call("cfd_timing_enable", 0)
     sweep_ms = ms.value / max(nsw.value, 1)
+    if ARGS.dump_outputs:
+        # the solve's result (every rank of a slab run: its owned planes)
+        res = {"phi": sj.owned() if use_slab and len(shape) == 3 else phi}
+        if gs:
+            res["iters_done"] = gs_done
+        dump_outputs(ARGS.dump_outputs, res, writers=world, suffix=f"_rank{rank}" if world > 1 else "")
 
     if use_slab:
         t = torch.tensor([elapsed, sweep_ms], dtype=torch.float64, device=coll_device(dist, dev))
@@ -686,7 +737,7 @@ def main():
                                               if gs else
                                               "bit-exact vs 1-GPU solve (96^3, ghost depths 1-4)")
                                              if verified else "MISMATCH")
-    if rank == 0 and world == 1 and not ARGS.no_cpu_baseline:
+    if rank == 0 and world == 1 and ARGS.full and not ARGS.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(shape, iters, gs)
         if len(shape) == 3:
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(shape, gs)

@@ -24,9 +24,9 @@ for s in "$@"; do
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step pytest_gpu 1000 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread ;;
     testsq) step pytest_gpu 900 python -m pytest tests -m gpu -q ;;
-    bench) step bench 600 python bench.py ;;
+    bench) step bench 600 python bench.py --full ;;
     bench512) step bench512 600 python bench.py --workload jacobi3d_512 --no-cpu-baseline ;;
-    bench2d) step bench2d 600 python bench.py --workload jacobi2d_8192_f64 ;;
+    bench2d) step bench2d 600 python bench.py --full --workload jacobi2d_8192_f64 ;;
     tiles) step tiles 900 python bench.py --steps 2 --warmup 1 --sweep-tiles --no-cpu-baseline ;;
     prof) step prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
     pmc_fetch) step pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --iters 30 --no-cpu-baseline ;;
@@ -36,15 +36,15 @@ for s in "$@"; do
     pmc_fetch_tb) step pmc_fetch_tb 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_tb -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --iters 20 --no-cpu-baseline ;;
     pmc_write_tb) step pmc_write_tb 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_tb -o run --output-format csv -- python3 bench.py --steps 1 --warmup 0 --iters 20 --no-cpu-baseline ;;
     prof_tb) step prof_tb 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_tb -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline ;;
-    slab1) step slab1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --force-slab --steps 3 --warmup 1 ;;
+    slab1) step slab1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 1 --force-slab --steps 3 --warmup 1 ;;
     benchch) step benchch 600 python bench.py --workload jacobi3d_channel --no-cpu-baseline ;;
     testsk) step pytest_k 900 python -m pytest tests -m gpu -q -k "k_levels or variants_agree or temporal or full_size" ;;
     ksweep) step ksweep 900 bash -c 'for cfg in ${KSWEEP:-"3 0 1 0" "3 16 2 0" "3 16 1 256" "4 0 1 0" "2 0 1 0"}; do set -- $cfg; echo "K=$1 rows=$2 PD=$3 zchunk=$4"; python bench.py --no-cpu-baseline --steps 5 --tb $1 --tb-rows $2 --tb-prefetch $3 --tb-zchunk $4 | grep -o "\"value\": [0-9.]*\|avg_launch_ms\": [0-9.]*" | tr "\n" " "; echo; done' ;;
     testspred) step pytest_pred 900 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread -k "predictor or powf or time_step or golden or persistent" ;;
-    benchpred) step benchpred 600 python bench.py --workload predictor2d_8192 --steps 20 --warmup 3 ;;
-    benchpred64) step benchpred64 600 python bench.py --workload predictor2d_8192_f64 --steps 20 --warmup 3 ;;
-    benchpredf) step benchpredf 600 python bench.py --workload predictor2d_8192 --steps 20 --warmup 3 --tau-mode fast ;;
-    benchpred64f) step benchpred64f 600 python bench.py --workload predictor2d_8192_f64 --steps 20 --warmup 3 --tau-mode fast ;;
+    benchpred) step benchpred 600 python bench.py --full --workload predictor2d_8192 --steps 20 --warmup 3 ;;
+    benchpred64) step benchpred64 600 python bench.py --full --workload predictor2d_8192_f64 --steps 20 --warmup 3 ;;
+    benchpredf) step benchpredf 600 python bench.py --full --workload predictor2d_8192 --steps 20 --warmup 3 --tau-mode fast ;;
+    benchpred64f) step benchpred64f 600 python bench.py --full --workload predictor2d_8192_f64 --steps 20 --warmup 3 --tau-mode fast ;;
     profpredf) step profpredf 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profpredf -o run --output-format csv -- python3 bench.py --workload predictor2d_8192 --steps 20 --warmup 3 --no-cpu-baseline --tau-mode fast ;;
     profpred64f) step profpred64f 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profpred64f -o run --output-format csv -- python3 bench.py --workload predictor2d_8192_f64 --steps 20 --warmup 3 --no-cpu-baseline --tau-mode fast ;;
     pmc_fetch_predf) step pmc_fetch_predf 300 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_predf -o run --output-format csv -- python3 bench.py --workload predictor2d_8192 --steps 12 --warmup 0 --no-cpu-baseline --tau-mode fast ;;
@@ -68,10 +68,10 @@ for s in "$@"; do
     sweep2d) step sweep2d 900 bash -c 'for K in ${K2D:-8 10 12}; do echo "K=$K"; python bench.py --workload jacobi2d_8192_f64 --no-cpu-baseline --steps 3 --tb $K | grep -o "\"value\": [0-9.]*\|avg_launch_ms\": [0-9.]*" | tr "\n" " "; echo; done' ;;
     testslocal) step pytest_local 900 python -m pytest tests -m gpu -q -x -k "local_group" ;;
     testsgs) step pytest_gs 900 python -m pytest tests -m gpu -q -k "rbgs or slab" ;;
-    benchgs) step benchgs 600 python bench.py --workload rbgs3d_1024 ;;
+    benchgs) step benchgs 600 python bench.py --full --workload rbgs3d_1024 ;;
     gssweep) step gssweep 900 bash -c 'for cfg in ${GSSWEEP:-0:0 2:16 4:0 4:16 2:18 2:20 2:28}; do set -- ${cfg/:/ }; echo "tb=$1 rows=$2"; python bench.py --workload rbgs3d_1024 --no-cpu-baseline --steps 3 --tb $1 --tb-rows $2 | grep -o "\"value\": [0-9.]*\|avg_launch_ms\": [0-9.]*\|iterations_done_last_step\": [0-9]*" | tr "\n" " "; echo; done' ;;
     benchgs_inplace) step benchgs_inplace 600 python bench.py --workload rbgs3d_1024 --tb 1 --no-cpu-baseline --steps 3 ;;
-    slab1gs) step slab1gs 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 1 --force-slab --workload rbgs3d_1024 --steps 3 --warmup 1 ;;
+    slab1gs) step slab1gs 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --full --gpus 1 --force-slab --workload rbgs3d_1024 --steps 3 --warmup 1 ;;
     prof2d) step prof2d 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof2d -o run --output-format csv -- python3 bench.py --workload jacobi2d_8192_f64 --steps 3 --warmup 1 --no-cpu-baseline ;;
     pmc_fetch_2d) step pmc_fetch_2d 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_2d -o run --output-format csv -- python3 bench.py --workload jacobi2d_8192_f64 --steps 1 --warmup 0 --iters 80 --no-cpu-baseline ;;
     pmc_write_2d) step pmc_write_2d 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_2d -o run --output-format csv -- python3 bench.py --workload jacobi2d_8192_f64 --steps 1 --warmup 0 --iters 80 --no-cpu-baseline ;;
@@ -98,10 +98,10 @@ for s in "$@"; do
     pmc_write_ch) step pmc_write_ch 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_ch -o run --output-format csv -- python3 bench.py --workload jacobi3d_channel --steps 1 --warmup 0 --iters 30 --no-cpu-baseline ;;
     prof512) step prof512 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof512 -o run --output-format csv -- python3 bench.py --workload jacobi3d_512 --steps 3 --warmup 1 --no-cpu-baseline ;;
     profch) step profch 600 rocprofv3 --kernel-trace --stats -d gpurun_out/profch -o run --output-format csv -- python3 bench.py --workload jacobi3d_channel --steps 3 --warmup 1 --no-cpu-baseline ;;
-    benchgs_n) step benchgs_n 600 python bench.py --workload rbgs3d_1024 --steps 5 ;;
-    bench512_n) step bench512_n 600 python bench.py --workload jacobi3d_512 ;;
-    benchch_n) step benchch_n 600 python bench.py --workload jacobi3d_channel ;;
-    benchcav) step benchcav 600 python bench.py --workload cavity2d_128 --steps 50 --warmup 5 ;;
+    benchgs_n) step benchgs_n 600 python bench.py --full --workload rbgs3d_1024 --steps 5 ;;
+    bench512_n) step bench512_n 600 python bench.py --full --workload jacobi3d_512 ;;
+    benchch_n) step benchch_n 600 python bench.py --full --workload jacobi3d_channel ;;
+    benchcav) step benchcav 600 python bench.py --full --workload cavity2d_128 --steps 50 --warmup 5 ;;
     prof_cyl) step prof_cyl 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_cyl -o run --output-format csv -- python3 scripts/cylinder_bench.py --steps 3 --warmup 1 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac

@@ -78,6 +78,39 @@ def test_shared_gpu_needs_one_device_and_copy_engines():
         bench.spawn_ranks(a, argv, run=fake_run, device_count=1)
 
 
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_whole_small_arrays_and_fixed_sample_of_large(tmp_path, monkeypatch):
+    """--dump-outputs: a small array is written whole in its own float type, an
+    integer as float64; an array past its share of the budget as the same
+    sample every time, within the budget."""
+    import numpy as np
+    import torch
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    done = torch.tensor([7], dtype=torch.int32)
+    bench.dump_outputs(tmp_path / "a", {"phi": small, "iters_done": done})
+    got = np.load(tmp_path / "a" / "phi.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy())
+    got = np.load(tmp_path / "a" / "iters_done.npy")
+    assert got.dtype == np.float64 and got.tolist() == [7.0]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    big = torch.arange(100 * 100, dtype=torch.float32).reshape(100, 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"u": big, "v": -big}, writers=2, suffix="_rank1")
+    u, v = np.load(tmp_path / "b" / "u_rank1.npy"), np.load(tmp_path / "b" / "v_rank1.npy")
+    assert u.dtype == np.float32 and u.shape == (256,) and u.nbytes + v.nbytes == 4096 // 2
+    assert np.array_equal(u, -v) and np.all(np.diff(u) >= 0) and len(np.unique(u)) > 200
+    assert np.array_equal(u, np.load(tmp_path / "c" / "u_rank1.npy"))
+
+
 def _gather_worker(rank, world, port, sizes, q):
     import os
     import torch

@@ -1,6 +1,6 @@
 """bench.py's N-rank path, end to end, on a one-GPU lease (--shared-gpu).
 
-`python bench.py --gpus 2 --shared-gpu ...` runs as a fresh child process: it
+`python bench.py --gpus 2 --shared-gpu --full ...` runs as a fresh child process: it
 spawns its two ranks (torch.distributed.run), puts both on device 0, joins a
 gloo process group, attaches the copy-engine transport (IPC-mapped neighbour
 ghosts, the N-GPU default), runs verify_slabs / verify_slabs_rbgs against the
@@ -23,7 +23,8 @@ pytestmark = pytest.mark.gpu
 
 
 def _run(args, timeout=420):
-    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--shared-gpu", "--no-cpu-baseline"] + args
+    cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--shared-gpu", "--full",
+           "--no-cpu-baseline"] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=str(ROOT))
     out = r.stdout + r.stderr
     assert r.returncode == 0, out[-6000:]
