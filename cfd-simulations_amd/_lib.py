@@ -51,6 +51,14 @@ PROTOTYPES = {
     "cfd_laplacian2d_f32": (c_int, [P, P, c_float, P, c_int, c_int, c_double, c_double, P]),
     "cfd_predictor2d_f32": (c_int, [P, P, P, c_float, P, P, P, c_int, c_int, c_double, c_double,
                                     c_float, c_int, P]),
+    "cfd_smagorinsky2d_f32": (c_int, [P, P, P, c_int, c_int, c_double, c_double, c_double, P]),
+    "cfd_predictor2d_les_f32": (c_int, [P, P, c_float, c_float, c_double, P, P, P, P, c_int, c_int, c_double,
+                                        c_double, c_float, c_int, P]),
+    "cfd_smagorinsky2d_f64": (c_int, [P, P, P, c_int, c_int, c_double, c_double, c_double, P]),
+    "cfd_predictor2d_les_f64": (c_int, [P, P, c_double, c_double, c_double, P, P, P, P, c_int, c_int, c_double,
+                                        c_double, c_double, c_int, P]),
+    "cfd_mean_f32": (c_int, [P, c_size_t, P, P]),
+    "cfd_mean_f64": (c_int, [P, c_size_t, P, P]),
     "cfd_set_predictor2d_config": (c_int, [c_int, c_int, c_int]),
     "cfd_set_predictor2d_tau_mode": (c_int, [c_int]),
     "cfd_get_predictor2d_tau_mode": (c_int, []),

@@ -373,6 +373,60 @@ __global__ __launch_bounds__(256) void k_energy_mean_mb(T *__restrict__ u, T *__
     }
 }
 
+// Mean of a[0..n) in float64 (np.mean(a, dtype=float64); the previous step's
+// nu_t in adaptive_time_step, v5.py:323) the way k_energy_mean_mb sums: block
+// b folds a fixed contiguous range thread-strided, the last block to take a
+// ticket adds the kEnergyBlocks partials in block order -- no atomics on the
+// sum, the same bits run to run.  ws: energy_scratch.
+template <typename T>
+__global__ __launch_bounds__(256) void k_mean_mb(const T *__restrict__ a, size_t n, double *out, unsigned *ws) {
+    constexpr int U = 8;
+    __shared__ double part[4];
+    __shared__ int last;
+    double *partial = reinterpret_cast<double *>(ws + 16);
+    const size_t per = (n + gridDim.x - 1) / gridDim.x;
+    const size_t b0 = blockIdx.x * per < n ? blockIdx.x * per : n, b1 = b0 + per < n ? b0 + per : n;
+    double s[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) s[q] = 0.0;
+    size_t c = b0 + threadIdx.x;
+    for (; c + (U - 1) * 256 < b1; c += U * 256) {
+        T x[U];
+#pragma unroll
+        for (int q = 0; q < U; ++q) x[q] = a[c + q * 256];
+#pragma unroll
+        for (int q = 0; q < U; ++q) s[q] += (double)x[q];
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q)
+        if (c + q * 256 < b1) s[q] += (double)a[c + q * 256];
+    double t = s[0];
+#pragma unroll
+    for (int q = 1; q < U; ++q) t += s[q];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, kWave);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+        __threadfence();  // the partial before the ticket
+        last = atomicAdd(ws, 1u) == (unsigned)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __shared__ double all[kEnergyBlocks];
+    __threadfence();
+    if ((int)threadIdx.x < (int)gridDim.x)
+        all[threadIdx.x] = __hip_atomic_load(partial + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = 0.0;
+        for (int k = 0; k < (int)gridDim.x; ++k) r += all[k];
+        *out = r / (double)n;
+        __hip_atomic_store(ws, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // apply_ibm_fast's factor on one cell (v5.py:228-237): float64 mask, float64
 // product, rounded to the field's type
 template <typename T>

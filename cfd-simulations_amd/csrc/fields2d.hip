@@ -88,19 +88,29 @@ __global__ void k_laplacian(const float *__restrict__ f, const float *__restrict
     lap[c] = r;
 }
 
+// compute_smagorinsky_viscosity_fast, v5.py:96-110 (smag_nut, pred_rows.hpp)
+__global__ void k_smagorinsky(const float *__restrict__ u, const float *__restrict__ v, float *__restrict__ nut,
+                              int ny, int nx, float cles, PredConst k) {
+    CFD_2D_INDEX
+    float r = 0.0f;
+    if (interior(i, j, ny, nx)) r = smag_nut(u[c], v[c], u[c + 1], v[c + 1], u[c + nx], v[c + nx], cles, k);
+    nut[c] = r;
+}
+
 // Fused predictor, v5.py:388-403: u* = u + dt*(-conv_u + lap_u), likewise v.
-template <bool SUPG>
+// LES: nu_eff holds nu_t and nu_eff = (nu_s + nu_t) + art per cell (v5.py:388).
+template <bool SUPG, bool LES = false>
 __global__ __launch_bounds__(256) void k_predictor(const float *__restrict__ u,
                                                    const float *__restrict__ v,
                                                    const float *__restrict__ nu_eff, float nu_s,
                                                    float *__restrict__ us, float *__restrict__ vs,
                                                    float *__restrict__ tau_out, int ny, int nx,
-                                                   float dt, PredConst k) {
+                                                   float dt, PredConst k, float art = 0.0f) {
     CFD_2D_INDEX
     const float uc = u[c], vc = v[c];
     float cu = 0.0f, cv = 0.0f, lu = 0.0f, lv = 0.0f, t = 0.0f;
     if (interior(i, j, ny, nx)) {
-        const float nu = nu_eff ? nu_eff[c] : nu_s;
+        const float nu = LES ? (nu_s + nu_eff[c]) + art : (nu_eff ? nu_eff[c] : nu_s);
         const float uE = u[c + 1], uW = u[c - 1], uN = u[c + nx], uS = u[c - nx];
         const float vE = v[c + 1], vW = v[c - 1], vN = v[c + nx], vS = v[c - nx];
         if (SUPG) {
@@ -925,14 +935,19 @@ int cfd_laplacian2d_f32(const float *phi, const float *nu_eff, float nu_eff_scal
     return CFD_OK;
 }
 
-int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, float nu_eff_scalar,
-                        float *u_star, float *v_star, float *tau, int ny, int nx, double dx,
-                        double dy, float dt, int use_supg, void *stream) {
-    CFD_REQUIRE(u && v && u_star && v_star, "predictor2d: null pointer");
+// cfd_predictor2d_f32 (les == false) and cfd_predictor2d_les_f32 (nu_eff null,
+// nu_s the molecular nu; nu_t may be null on the row march)
+static int predictor2d_f32(const char *who, const float *u, const float *v, const float *nu_eff, float nu_s,
+                           float *u_star, float *v_star, float *tau, int ny, int nx, double dx, double dy, float dt,
+                           int use_supg, void *stream, bool les, float art, double cs, float *nu_t) {
+    CFD_REQUIRE(u && v && u_star && v_star, "%s: null pointer", who);
     CFD_REQUIRE(u_star != u && v_star != v && u_star != v && v_star != u,
-                "predictor2d: outputs must not alias inputs");
+                "%s: outputs must not alias inputs", who);
+    CFD_REQUIRE(!nu_t || (nu_t != u && nu_t != v && nu_t != u_star && nu_t != v_star && nu_t != tau),
+                "%s: nu_t must not alias another array", who);
     CFD_SHAPE2D(ny, nx);
     const PredConst k = make_pred_const(dx, dy);
+    const float cles = les ? (float)smag_const(cs, dx, dy) : 0.0f;
     hipStream_t s = as_stream(stream);
     // cells per lane of the row march: the preferred count (tuning; default
     // 2), halved until nx and every array's alignment allow it (1 always does)
@@ -940,13 +955,16 @@ int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, flo
     auto fits = [&](int w) {
         const uintptr_t m = (uintptr_t)(4 * w - 1);
         auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
-        return nx % w == 0 && al(u) && al(v) && al(u_star) && al(v_star) && al(tau) && al(nu_eff);
+        return nx % w == 0 && al(u) && al(v) && al(u_star) && al(v_star) && al(tau) && al(nu_eff) && al(nu_t);
     };
     while (vec > 1 && !fits(vec)) vec /= 2;
     const bool rows_ok = (size_t)ny * nx * sizeof(float) < ((size_t)1 << 31);
+    const bool rows = tuning().pred_variant != 1 && rows_ok;
+    CFD_REQUIRE(!les || rows || nu_t, "%s: the one-thread-per-cell path needs nu_t (it stores it, then reads it)",
+                who);
     const int tau_mode = use_supg ? tuning().pred_tau : kTauExact;
     const int tk = timing_begin(s, kTimingPredictor);
-    if (tuning().pred_variant != 1 && rows_ok) {
+    if (rows) {
         PredRowArgs<float> a;
         a.u = u;
         a.v = v;
@@ -954,23 +972,62 @@ int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, flo
         a.us = u_star;
         a.vs = v_star;
         a.tau = tau;  // zeros without SUPG
-        a.nu_s = nu_eff_scalar;
+        a.nu_s = nu_s;
         a.dt = dt;
         a.ny = ny;
         a.nx = nx;
         a.k = k;
+        a.les = les;
+        a.nut = nu_t;
+        a.art = art;
+        a.cles = cles;
         CFD_CHECK_HIP(pred_rows_launch<float>(a, use_supg != 0, tau_mode, vec, tuning().pred_rows, s));
         set_last_predictor(1, tau_mode, vec);
+    } else if (les) {
+        // the stand-alone nu_t pass, then nu_eff per cell from the stored nu_t
+        hipLaunchKernelGGL(k_smagorinsky, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_t, ny, nx, cles, k);
+        if (use_supg)
+            hipLaunchKernelGGL((k_predictor<true, true>), grid2d(ny, nx), dim3(256), 0, s, u, v, (const float *)nu_t,
+                               nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
+        else
+            hipLaunchKernelGGL((k_predictor<false, true>), grid2d(ny, nx), dim3(256), 0, s, u, v, (const float *)nu_t,
+                               nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
+        set_last_predictor(0, kTauExact, 1);
     } else if (use_supg) {
-        hipLaunchKernelGGL(k_predictor<true>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_eff_scalar, u_star,
-                           v_star, tau, ny, nx, dt, k);
+        hipLaunchKernelGGL(k_predictor<true>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s, u_star,
+                           v_star, tau, ny, nx, dt, k, 0.0f);
         set_last_predictor(0, kTauExact, 1);
     } else {
-        hipLaunchKernelGGL(k_predictor<false>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_eff_scalar, u_star,
-                           v_star, tau, ny, nx, dt, k);
+        hipLaunchKernelGGL(k_predictor<false>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s, u_star,
+                           v_star, tau, ny, nx, dt, k, 0.0f);
         set_last_predictor(0, kTauExact, 1);
     }
     timing_end(tk, s, 1);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, float nu_eff_scalar,
+                        float *u_star, float *v_star, float *tau, int ny, int nx, double dx,
+                        double dy, float dt, int use_supg, void *stream) {
+    return predictor2d_f32("predictor2d", u, v, nu_eff, nu_eff_scalar, u_star, v_star, tau, ny, nx, dx, dy, dt,
+                           use_supg, stream, false, 0.0f, 0.0, nullptr);
+}
+
+int cfd_predictor2d_les_f32(const float *u, const float *v, float nu, float art_visc, double cs, float *u_star,
+                            float *v_star, float *tau, float *nu_t, int ny, int nx, double dx, double dy, float dt,
+                            int use_supg, void *stream) {
+    return predictor2d_f32("predictor2d_les", u, v, nullptr, nu, u_star, v_star, tau, ny, nx, dx, dy, dt, use_supg,
+                           stream, true, art_visc, cs, nu_t);
+}
+
+int cfd_smagorinsky2d_f32(const float *u, const float *v, float *nu_t, int ny, int nx, double dx, double dy,
+                          double cs, void *stream) {
+    CFD_REQUIRE(u && v && nu_t, "smagorinsky2d: null pointer");
+    CFD_REQUIRE(nu_t != u && nu_t != v, "smagorinsky2d: nu_t must not alias an input");
+    CFD_SHAPE2D(ny, nx);
+    hipLaunchKernelGGL(k_smagorinsky, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, nu_t, ny, nx,
+                       (float)smag_const(cs, dx, dy), make_pred_const(dx, dy));
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }
@@ -1233,6 +1290,16 @@ int cfd_energy_mean2d_f32(const float *u, const float *v, size_t n, double *out,
     CFD_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(double), s));
     hipLaunchKernelGGL(k_energy_sum, dim3(grid1d(n)), dim3(256), 0, s, u, v, n, out);
     hipLaunchKernelGGL(k_scale_double, dim3(1), dim3(1), 0, s, out, 1.0 / (double)n);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_mean_f32(const float *a, size_t n, double *out, void *stream) {
+    CFD_REQUIRE(a && out && n > 0, "mean_f32: bad arguments");
+    hipStream_t s = as_stream(stream);
+    unsigned *ws = energy_scratch(s);
+    CFD_REQUIRE(ws, "mean_f32: no scratch for the partial sums");
+    hipLaunchKernelGGL(k_mean_mb<float>, dim3(kEnergyBlocks), dim3(256), 0, s, a, n, out, ws);
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

@@ -120,18 +120,28 @@ __global__ void k_component64(int kind, const double *__restrict__ u, const doub
     out[c] = r;
 }
 
-// Fused predictor, v5.py:388-403: u* = u + dt*(-conv_u + lap_u), likewise v
-template <bool SUPG>
+// compute_smagorinsky_viscosity_fast, v5.py:96-110 (smag_nut, pred_rows.hpp)
+__global__ void k_smagorinsky64(const double *__restrict__ u, const double *__restrict__ v,
+                                double *__restrict__ nut, int ny, int nx, double cles, PredK<double> k) {
+    CFD_2D_INDEX64
+    double r = 0.0;
+    if (interior64(i, j, ny, nx)) r = smag_nut(u[c], v[c], u[c + 1], v[c + 1], u[c + nx], v[c + nx], cles, k);
+    nut[c] = r;
+}
+
+// Fused predictor, v5.py:388-403: u* = u + dt*(-conv_u + lap_u), likewise v.
+// LES: nu_eff holds nu_t and nu_eff = (nu_s + nu_t) + art per cell (v5.py:388).
+template <bool SUPG, bool LES = false>
 __global__ __launch_bounds__(256) void k_predictor64(const double *__restrict__ u, const double *__restrict__ v,
                                                      const double *__restrict__ nu_eff, double nu_s,
                                                      double *__restrict__ us, double *__restrict__ vs,
                                                      double *__restrict__ tau_out, int ny, int nx, double dt,
-                                                     Pred64 k) {
+                                                     Pred64 k, double art = 0.0) {
     CFD_2D_INDEX64
     const double uc = u[c], vc = v[c];
     double cu = 0.0, cv = 0.0, lu = 0.0, lv = 0.0, t = 0.0;
     if (interior64(i, j, ny, nx)) {
-        const double nu = nu_eff ? nu_eff[c] : nu_s;
+        const double nu = LES ? (nu_s + nu_eff[c]) + art : (nu_eff ? nu_eff[c] : nu_s);
         const double uE = u[c + 1], uW = u[c - 1], uN = u[c + nx], uS = u[c - nx];
         const double vE = v[c + 1], vW = v[c - 1], vN = v[c + nx], vS = v[c - nx];
         if (SUPG) {
@@ -498,27 +508,35 @@ int cfd_laplacian2d_f64(const double *phi, const double *nu_eff, double nu_eff_s
     return CFD_OK;
 }
 
-int cfd_predictor2d_f64(const double *u, const double *v, const double *nu_eff, double nu_eff_scalar,
-                        double *u_star, double *v_star, double *tau, int ny, int nx, double dx, double dy, double dt,
-                        int use_supg, void *stream) {
-    CFD_REQUIRE(u && v && u_star && v_star, "predictor2d_f64: null pointer");
+// cfd_predictor2d_f64 (les == false) and cfd_predictor2d_les_f64 (nu_eff null,
+// nu_s the molecular nu; nu_t may be null on the row march)
+static int predictor2d_f64(const char *who, const double *u, const double *v, const double *nu_eff, double nu_s,
+                           double *u_star, double *v_star, double *tau, int ny, int nx, double dx, double dy,
+                           double dt, int use_supg, void *stream, bool les, double art, double cs, double *nu_t) {
+    CFD_REQUIRE(u && v && u_star && v_star, "%s: null pointer", who);
     CFD_REQUIRE(u_star != u && v_star != v && u_star != v && v_star != u,
-                "predictor2d_f64: outputs must not alias inputs");
+                "%s: outputs must not alias inputs", who);
+    CFD_REQUIRE(!nu_t || (nu_t != u && nu_t != v && nu_t != u_star && nu_t != v_star && nu_t != tau),
+                "%s: nu_t must not alias another array", who);
     CFD_SHAPE2D64(ny, nx);
     hipStream_t s = as_stream(stream);
+    const double cles = les ? smag_const(cs, dx, dy) : 0.0;
     // the row march (pred_rows.hpp): cells per lane 2 (16 B) or 1, halved
     // until nx and every array's alignment allow it
     int vec = tuning().pred_vec == 1 ? 1 : 2;
     auto fits = [&](int w) {
         const uintptr_t m = (uintptr_t)(8 * w - 1);
         auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
-        return nx % w == 0 && al(u) && al(v) && al(u_star) && al(v_star) && al(tau) && al(nu_eff);
+        return nx % w == 0 && al(u) && al(v) && al(u_star) && al(v_star) && al(tau) && al(nu_eff) && al(nu_t);
     };
     while (vec > 1 && !fits(vec)) vec /= 2;
     const bool rows_ok = (size_t)ny * nx * sizeof(double) < ((size_t)1 << 31) && fits(vec);
+    const bool rows = tuning().pred_variant != 1 && rows_ok;
+    CFD_REQUIRE(!les || rows || nu_t, "%s: the one-thread-per-cell path needs nu_t (it stores it, then reads it)",
+                who);
     const int tau_mode = use_supg ? tuning().pred_tau : kTauExact;
     const int tk = timing_begin(s, kTimingPredictor);
-    if (tuning().pred_variant != 1 && rows_ok) {
+    if (rows) {
         PredRowArgs<double> a;
         a.u = u;
         a.v = v;
@@ -526,24 +544,74 @@ int cfd_predictor2d_f64(const double *u, const double *v, const double *nu_eff, 
         a.us = u_star;
         a.vs = v_star;
         a.tau = tau;  // zeros without SUPG
-        a.nu_s = nu_eff_scalar;
+        a.nu_s = nu_s;
         a.dt = dt;
         a.ny = ny;
         a.nx = nx;
         a.k = make_pred_k<double>(dx, dy);
+        a.les = les;
+        a.nut = nu_t;
+        a.art = art;
+        a.cles = cles;
         CFD_CHECK_HIP(pred_rows_launch<double>(a, use_supg != 0, tau_mode, vec, tuning().pred_rows, s));
         set_last_predictor(1, tau_mode, vec);
     } else {
         const Pred64 k = make_pred64(dx, dy);
-        if (use_supg)
-            hipLaunchKernelGGL(k_predictor64<true>, grid2d64(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_eff_scalar,
-                               u_star, v_star, tau, ny, nx, dt, k);
-        else
-            hipLaunchKernelGGL(k_predictor64<false>, grid2d64(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_eff_scalar,
-                               u_star, v_star, tau, ny, nx, dt, k);
+        if (les) {
+            // the stand-alone nu_t pass, then nu_eff per cell from the stored nu_t
+            hipLaunchKernelGGL(k_smagorinsky64, grid2d64(ny, nx), dim3(256), 0, s, u, v, nu_t, ny, nx, cles,
+                               make_pred_k<double>(dx, dy));
+            if (use_supg)
+                hipLaunchKernelGGL((k_predictor64<true, true>), grid2d64(ny, nx), dim3(256), 0, s, u, v,
+                                   (const double *)nu_t, nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
+            else
+                hipLaunchKernelGGL((k_predictor64<false, true>), grid2d64(ny, nx), dim3(256), 0, s, u, v,
+                                   (const double *)nu_t, nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
+        } else if (use_supg) {
+            hipLaunchKernelGGL(k_predictor64<true>, grid2d64(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s,
+                               u_star, v_star, tau, ny, nx, dt, k, 0.0);
+        } else {
+            hipLaunchKernelGGL(k_predictor64<false>, grid2d64(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s,
+                               u_star, v_star, tau, ny, nx, dt, k, 0.0);
+        }
         set_last_predictor(0, kTauExact, 1);
     }
     timing_end(tk, s, 1);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_predictor2d_f64(const double *u, const double *v, const double *nu_eff, double nu_eff_scalar,
+                        double *u_star, double *v_star, double *tau, int ny, int nx, double dx, double dy, double dt,
+                        int use_supg, void *stream) {
+    return predictor2d_f64("predictor2d_f64", u, v, nu_eff, nu_eff_scalar, u_star, v_star, tau, ny, nx, dx, dy, dt,
+                           use_supg, stream, false, 0.0, 0.0, nullptr);
+}
+
+int cfd_predictor2d_les_f64(const double *u, const double *v, double nu, double art_visc, double cs, double *u_star,
+                            double *v_star, double *tau, double *nu_t, int ny, int nx, double dx, double dy,
+                            double dt, int use_supg, void *stream) {
+    return predictor2d_f64("predictor2d_les_f64", u, v, nullptr, nu, u_star, v_star, tau, ny, nx, dx, dy, dt,
+                           use_supg, stream, true, art_visc, cs, nu_t);
+}
+
+int cfd_smagorinsky2d_f64(const double *u, const double *v, double *nu_t, int ny, int nx, double dx, double dy,
+                          double cs, void *stream) {
+    CFD_REQUIRE(u && v && nu_t, "smagorinsky2d_f64: null pointer");
+    CFD_REQUIRE(nu_t != u && nu_t != v, "smagorinsky2d_f64: nu_t must not alias an input");
+    CFD_SHAPE2D64(ny, nx);
+    hipLaunchKernelGGL(k_smagorinsky64, grid2d64(ny, nx), dim3(256), 0, as_stream(stream), u, v, nu_t, ny, nx,
+                       smag_const(cs, dx, dy), make_pred_k<double>(dx, dy));
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_mean_f64(const double *a, size_t n, double *out, void *stream) {
+    CFD_REQUIRE(a && out && n > 0, "mean_f64: bad arguments");
+    hipStream_t s = as_stream(stream);
+    unsigned *ws = energy_scratch(s);
+    CFD_REQUIRE(ws, "mean_f64: no scratch for the partial sums");
+    hipLaunchKernelGGL(k_mean_mb<double>, dim3(kEnergyBlocks), dim3(256), 0, s, a, n, out, ws);
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

@@ -39,7 +39,19 @@
 //   L-infinity of the exact mode (tests/test_gpu_predictor.py measures it).
 // Everything else is k_predictor's arithmetic operation for operation, so the
 // exact mode is bit-identical to the per-cell kernels.
+//
+// Viscosity modes (PredNu): a scalar nu_eff, a nu_eff array (one more row load
+// per field row), or LES (kNuLes, use_les=True, v5.py:381-388): the Smagorinsky
+// nu_t of the lane's cells (smag_nut: forward differences to the east and
+// north neighbours) is formed in the march from registers it already holds --
+// Uc / Vc, the east neighbours uE / vE (DPP shift, segment-halo cell) and row
+// i + 1 (Up / Vp) -- so it costs no HBM read; nu_eff = (nu + nu_t) + art_visc
+// then feeds tau, the Laplacian and the packed path exactly where the array
+// mode's loaded value does, and nu_t leaves with tau's streaming store (0 on
+// the ring): 24 B per float cell, 48 B per double cell with tau and nu_t.
 #pragma once
+#include <cmath>
+
 #include "common.hpp"
 #include "libm_pow.hpp"
 #include "libm_powf.hpp"
@@ -47,6 +59,7 @@
 namespace cfd {
 
 enum PredTau { kTauExact = 0, kTauFast = 1 };
+enum PredNu { kNuScalar = 0, kNuArray = 1, kNuLes = 2 };
 
 // stencil constants (Python floats rounded to T where they meet T data, NEP 50)
 template <typename T>
@@ -126,6 +139,29 @@ __device__ inline T laplacian(T nu, T C, T E, T W, T N, T S, const PredK<T> &k) 
     const T l1 = ((E - T(2) * C) + W) * k.lx;
     const T l2 = ((N - T(2) * C) + S) * k.ly;
     return nu * (l1 + l2);
+}
+
+// sqrt(q), correctly rounded over the whole range (subnormal q included: HIP's
+// default IEEE sqrt, scaled where v_sqrt_f32 alone would not do)
+__device__ inline float sqrt_ieee(float q) { return __builtin_sqrtf(q); }
+__device__ inline double sqrt_ieee(double q) { return __builtin_sqrt(q); }
+// compute_smagorinsky_viscosity_fast body (v5.py:96-110) for one interior
+// cell: forward-difference strain rate from the cell (uc, vc), its east (uE,
+// vE) and north (uN, vN: row i + 1) neighbours; cles = T((Cs sqrt(dx dy))^2)
+template <typename T>
+__device__ inline T smag_nut(T uc, T vc, T uE, T vE, T uN, T vN, T cles, const PredK<T> &k) {
+    const T dudx = (uE - uc) * k.ux, dudy = (uN - uc) * k.uy;
+    const T dvdx = (vE - vc) * k.ux, dvdy = (vN - vc) * k.uy;
+    const T sh = dudy + dvdx;
+    const T q = T(2) * (dudx * dudx + dvdy * dvdy) + sh * sh;
+    return cles * sqrt_ieee(q);
+}
+// (Cs * sqrt(dx*dy))**2 in Python floats: `**` on a Python float is libm's pow
+// (the exponent is kept opaque so the compiler cannot turn it into a product,
+// which need not round the same way); the caller rounds it to T once
+inline double smag_const(double cs, double dx, double dy) {
+    volatile double two = 2.0;
+    return std::pow(cs * std::sqrt(dx * dy), two);
 }
 
 // a / b, correctly rounded, from rb ~ 1/b (v_rcp_f32) and one Newton step:
@@ -258,9 +294,14 @@ template <typename T>
 struct PredRowArgs {
     const T *u, *v, *nu;  // nu: the nu_eff array, or null (nu_s)
     T *us, *vs, *tau;     // tau: null = not written
-    T nu_s, dt;
+    T nu_s, dt;           // (LES: nu_s is the molecular nu)
     int ny, nx, rows, nseg, groups;
     PredK<T> k;
+    // LES (kNuLes): nu_t out (null = not written), the artificial viscosity
+    // and T((Cs sqrt(dx dy))**2)
+    T *nut = nullptr;
+    T art = T(0), cles = T(0);
+    bool les = false;
 };
 
 // a lane's VEC cells of one row
@@ -303,9 +344,11 @@ __device__ inline T pld1(__amdgpu_buffer_rsrc_t r, uint32_t ofs) {
     return pldv<T, 1>(r, ofs).x[0];
 }
 
-template <typename T, int TAU, bool SUPG, bool NUA, int VEC>
+template <typename T, int TAU, bool SUPG, int NU, int VEC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_predictor_rows(PredRowArgs<T> a) {
     using M = PredMath<T>;
+    constexpr bool NUA = NU == kNuArray, LES = NU == kNuLes;
+    constexpr bool NUV = NUA || LES;  // nu_eff varies per cell
     constexpr bool kExactTau = SUPG && TAU == kTauExact;
     constexpr int SW = 64 * VEC;  // segment width (columns)
     const int lane = threadIdx.x & (kWave - 1);
@@ -336,6 +379,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
     const __amdgpu_buffer_rsrc_t rus = __builtin_amdgcn_make_buffer_rsrc(a.us, 0, bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rvs = __builtin_amdgcn_make_buffer_rsrc(a.vs, 0, bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(a.tau ? a.tau : a.us, 0, a.tau ? bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rnt =
+        __builtin_amdgcn_make_buffer_rsrc(LES && a.nut ? a.nut : a.us, 0, LES && a.nut ? bytes : 0, 0x00020000);
     // byte offset of this lane's cells in row i (kOob outside the grid: reads 0, stores dropped)
     auto rofs = [&](int i) -> uint32_t {
         return ((i >= 0) & (i < ny) & lane_in) ? (uint32_t)(((size_t)i * nx + x0) * sizeof(T)) : kOob;
@@ -372,7 +417,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
         const T HUn = pld1<T>(ru, hofs(i + 2)), HVn = pld1<T>(rv, hofs(i + 2));
         Cells<T, VEC> NUn = {};
         if (NUA) NUn = pldv<T, VEC>(rn, rofs(i + 2));
-        Cells<T, VEC> uo = Uc, vo = Vc, to = {};
+        Cells<T, VEC> uo = Uc, vo = Vc, to = {}, nto = {};
         if (i >= 1 && i <= ny - 2) {  // wave-uniform: boundary rows keep u* = u + dt*(-0 + 0)
             const T *uc = Uc.x, *vc = Vc.x;
             T uE[VEC], uW[VEC], vE[VEC], vW[VEC];
@@ -382,6 +427,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
                 uW[c] = c > 0 ? uc[c - 1] : dpp_from_lower_old(HUc, uc[VEC - 1]);
                 vE[c] = c < VEC - 1 ? vc[c + 1] : dpp_from_upper_old(HVc, vc[0]);
                 vW[c] = c > 0 ? vc[c - 1] : dpp_from_lower_old(HVc, vc[VEC - 1]);
+            }
+            // nu_eff of the lane's cells: the loaded row, or (LES) nu_t formed
+            // here, 0 on the side columns, then (nu + nu_t) + art_visc
+            T nuv[VEC];
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) {
+                nuv[c] = NUA ? NUc.x[c] : a.nu_s;
+                if constexpr (LES) {
+                    const bool in = x0 + c >= 1 && x0 + c <= nx - 2;
+                    const T nt = smag_nut(uc[c], vc[c], uE[c], vE[c], Up.x[c], Vp.x[c], a.cles, a.k);
+                    nto.x[c] = in ? nt : T(0);
+                    nuv[c] = (a.nu_s + nto.x[c]) + a.art;
+                }
             }
             T tq[VEC];
             if constexpr (kExactTau) {
@@ -439,16 +497,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
                 }
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) {
-                    const T nu = NUA ? NUc.x[c] : a.nu_s;
-                    tq[c] = M::tau_exact(vmq[c], nu, NUA ? M::rcp(nu + a.k.eps) : rnu_s, dt, a.k);
+                    const T nu = nuv[c];
+                    tq[c] = M::tau_exact(vmq[c], nu, NUV ? M::rcp(nu + a.k.eps) : rnu_s, dt, a.k);
                 }
             } else if constexpr (SUPG) {
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) {
                     const T vm = M::sqrt_rn(uc[c] * uc[c] + vc[c] * vc[c]);
                     T b2 = b2_s, rb2 = rb2_s;
-                    if (NUA) {
-                        b2 = T(2) * (NUc.x[c] + a.k.eps);
+                    if (NUV) {
+                        b2 = T(2) * (nuv[c] + a.k.eps);
                         rb2 = M::rcp(b2);
                     }
                     tq[c] = M::tau_tol(vm, b2, rb2, dt, a.k);
@@ -475,9 +533,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
                 f2 cdu = csu - t * (U * (ux2 * a.k.c2x) + V * (uy2 * a.k.c2y));
                 f2 cdv = csv - t * (U * (vx2 * a.k.c2x) + V * (vy2 * a.k.c2y));
                 asm volatile("" : "+v"(cdu), "+v"(cdv));  // formed unconditionally (conv_supg_sel)
-                const f2 NU = NUA ? f2{NUc.x[0], NUc.x[1]} : f2{a.nu_s, a.nu_s};
-                const f2 lu = NU * (ux2 * a.k.lx + uy2 * a.k.ly);
-                const f2 lv = NU * (vx2 * a.k.lx + vy2 * a.k.ly);
+                const f2 NU2 = {nuv[0], nuv[1]};
+                const f2 lu = NU2 * (ux2 * a.k.lx + uy2 * a.k.ly);
+                const f2 lv = NU2 * (vx2 * a.k.lx + vy2 * a.k.ly);
                 const bool in0 = x0 >= 1 && x0 <= nx - 2, in1 = x0 + 1 >= 1 && x0 + 1 <= nx - 2;
                 // a face cell: conv = lap = tau = 0 (np.zeros_like rings)
                 const f2 cu = {in0 && t.x > 0.0f ? cdu.x : (in0 ? csu.x : 0.0f),
@@ -496,7 +554,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
             } else {
 #pragma unroll
             for (int c = 0; c < VEC; ++c) {
-                const T nu = NUA ? NUc.x[c] : a.nu_s;
+                const T nu = nuv[c];
                 T cu, cv, t = T(0);
                 if constexpr (SUPG) {
                     t = tq[c];
@@ -526,6 +584,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
         pstv<T, VEC>(uo, rus, o);
         pstv<T, VEC>(vo, rvs, o);
         if (a.tau) pstv<T, VEC>(to, rt, o);  // zeros without SUPG (v5.py:292)
+        if constexpr (LES) {
+            if (a.nut) pstv<T, VEC>(nto, rnt, o);  // zeros on the ring (np.zeros_like)
+        }
         Um = Uc;
         Vm = Vc;
         Uc = Up;
@@ -543,15 +604,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) voi
     }
 }
 
-// The row-march kernel for (tau mode, SUPG, array nu, cells per lane)
+// The row-march kernel for (tau mode, SUPG, viscosity mode, cells per lane)
+template <typename T, int TAU, bool SUPG, int VEC>
+inline const void *pred_rows_kernel_nu(int nu) {
+    if (nu == kNuLes) return (const void *)k_predictor_rows<T, TAU, SUPG, kNuLes, VEC>;
+    return nu == kNuArray ? (const void *)k_predictor_rows<T, TAU, SUPG, kNuArray, VEC>
+                          : (const void *)k_predictor_rows<T, TAU, SUPG, kNuScalar, VEC>;
+}
 template <typename T, int VEC>
-inline const void *pred_rows_kernel_v(bool supg, int tau, bool nua) {
-    if (!supg) return nua ? (const void *)k_predictor_rows<T, kTauExact, false, true, VEC>
-                          : (const void *)k_predictor_rows<T, kTauExact, false, false, VEC>;
-    if (tau == kTauFast) return nua ? (const void *)k_predictor_rows<T, kTauFast, true, true, VEC>
-                                    : (const void *)k_predictor_rows<T, kTauFast, true, false, VEC>;
-    return nua ? (const void *)k_predictor_rows<T, kTauExact, true, true, VEC>
-               : (const void *)k_predictor_rows<T, kTauExact, true, false, VEC>;
+inline const void *pred_rows_kernel_v(bool supg, int tau, int nu) {
+    if (!supg) return pred_rows_kernel_nu<T, kTauExact, false, VEC>(nu);
+    if (tau == kTauFast) return pred_rows_kernel_nu<T, kTauFast, true, VEC>(nu);
+    return pred_rows_kernel_nu<T, kTauExact, true, VEC>(nu);
 }
 
 // workgroups of kernel f resident on the current device at once, cached per
@@ -568,13 +632,14 @@ void set_last_predictor(int path, int tau, int vec);
 template <typename T>
 hipError_t pred_rows_launch(PredRowArgs<T> a, bool supg, int tau, int vec, int rows, hipStream_t s) {
     const void *f;
+    const int nu = a.les ? kNuLes : (a.nu != nullptr ? kNuArray : kNuScalar);
     if (vec == 4) {
-        if constexpr (sizeof(T) == 4) f = pred_rows_kernel_v<T, 4>(supg, tau, a.nu != nullptr);
+        if constexpr (sizeof(T) == 4) f = pred_rows_kernel_v<T, 4>(supg, tau, nu);
         else return hipErrorInvalidValue;
     } else if (vec == 2) {
-        f = pred_rows_kernel_v<T, 2>(supg, tau, a.nu != nullptr);
+        f = pred_rows_kernel_v<T, 2>(supg, tau, nu);
     } else {
-        f = pred_rows_kernel_v<T, 1>(supg, tau, a.nu != nullptr);
+        f = pred_rows_kernel_v<T, 1>(supg, tau, nu);
     }
     a.nseg = ceil_div(a.nx, 64 * vec);
     a.groups = ceil_div(a.nseg, 4);

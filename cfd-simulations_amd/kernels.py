@@ -21,6 +21,7 @@ __all__ = [
     "compute_laplacian_fast", "compute_divergence_fast", "compute_gradient_fast",
     "solve_pressure_gauss_seidel_fast", "solve_pressure_jacobi", "apply_ibm_fast",
     "clean_divergence_fast", "predictor_fused", "project_velocity", "solve_pressure_jacobi3d",
+    "compute_smagorinsky_viscosity_fast", "predictor_fused_les", "mean64",
     "solve_pressure_jacobi3d_zero",
     "solve_pressure_gauss_seidel3d", "persistent_failures",
 ]
@@ -93,6 +94,31 @@ def _nu(nu_eff, dtype=torch.float32):
             raise TypeError(f"nu_eff must be {dtype}, got {nu_eff.dtype}")
         return nu_eff.contiguous(), 0.0
     return None, float(np.float32(nu_eff)) if dtype == torch.float32 else float(nu_eff)
+
+
+def compute_smagorinsky_viscosity_fast(u, v, dx, dy, cs, out=None):
+    """v5.py:96-110: the Smagorinsky eddy viscosity nu_t = (cs sqrt(dx dy))**2 |S|
+    from forward differences, 0 on the boundary ring.  ``out``: an optional
+    array of u's shape and dtype to write into.  Returns nu_t."""
+    ny, nx = _shape2d(u)
+    _like(u, v, "v")
+    nu_t = torch.empty_like(u) if out is None else _like(u, out, "out")
+    call(_fields("cfd_smagorinsky2d", u, v, nu_t), ptr(u), ptr(v), ptr(nu_t), ny, nx, float(dx), float(dy),
+         float(cs), stream_handle())
+    return nu_t
+
+
+def mean64(a, out=None):
+    """np.mean(a, dtype=np.float64) of a float32 / float64 device array into a
+    float64 device scalar (``out``: a 1-element float64 tensor, allocated if
+    omitted), without a host read; partial sums in a fixed order, the same
+    bits run to run.  Returns ``out``."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=a.device)
+    if out.dtype != torch.float64 or out.numel() != 1:
+        raise TypeError("mean64: out must be one float64 element")
+    call(_fields("cfd_mean", a), ptr(a), int(a.numel()), ptr(out), stream_handle())
+    return out
 
 
 def compute_supg_stabilization_fast(u, v, dx, dy, dt, nu_eff):
@@ -285,6 +311,51 @@ def clean_divergence_fast(u, v, dx, dy, iterations=2, workspace=None):
 TAU_MODES = {"exact": 0, "fast": 1}
 
 
+def _with_tau_mode(tau_mode, fn):
+    """Run fn() under tau_mode ("exact" / "fast"; None: the thread's current
+    setting), restoring the calling thread's setting afterwards."""
+    prev = None
+    if tau_mode is not None:
+        prev = int(lib().cfd_get_predictor2d_tau_mode())
+        if prev != TAU_MODES[tau_mode]:
+            call("cfd_set_predictor2d_tau_mode", TAU_MODES[tau_mode])
+        else:
+            prev = None
+    try:
+        fn()
+    finally:
+        if prev is not None:
+            call("cfd_set_predictor2d_tau_mode", prev)
+
+
+def predictor_fused_les(u, v, dx, dy, dt, nu, art_visc, cs, use_supg=True, u_star=None, v_star=None, tau=None,
+                        nu_t=None, tau_mode=None):
+    """The LES predictor (use_les=True, v5.py:381-403) in one pass: nu_t =
+    compute_smagorinsky_viscosity_fast(u, v, dx, dy, cs), nu_eff = (nu + nu_t)
+    + art_visc per cell in the fields' dtype, then predictor_fused's
+    arithmetic -- the same bits as those calls, with nu_t formed in the row
+    march's registers.  Returns (u_star, v_star, tau, nu_t).  ``nu_t`` None:
+    nu_t is not stored (the row march only; the one-thread-per-cell path
+    needs the array and raises).  tau_mode: as in predictor_fused."""
+    ny, nx = _shape2d(u)
+    if tau_mode is not None and tau_mode not in TAU_MODES:
+        raise ValueError(f"tau_mode must be one of {sorted(TAU_MODES)}, not {tau_mode!r}")
+    us = torch.empty_like(u) if u_star is None else u_star
+    vs = torch.empty_like(v) if v_star is None else v_star
+    if tau is None and use_supg:
+        tau = torch.empty_like(u)
+    nt = nu_t
+    for t, name in ((v, "v"), (us, "u_star"), (vs, "v_star"), (tau, "tau"), (nt, "nu_t")):
+        _like(u, t, name)
+    f32 = u.dtype == torch.float32
+    sc = (lambda x: float(np.float32(x))) if f32 else float
+    _with_tau_mode(tau_mode, lambda: call(
+        _fields("cfd_predictor2d_les", u, v, us, vs, tau, nt), ptr(u), ptr(v), sc(nu), sc(art_visc), float(cs),
+        ptr(us), ptr(vs), ptr(tau), ptr(nt), ny, nx, float(dx), float(dy), _dt_arg(dt, u.dtype),
+        int(bool(use_supg)), stream_handle()))
+    return us, vs, tau, nt
+
+
 def predictor_fused(u, v, dx, dy, dt, nu_eff, use_supg=True, u_star=None, v_star=None, tau=None, tau_mode=None):
     """v5.py:388-403 in one pass: returns (u_star, v_star, tau).
 
@@ -303,20 +374,9 @@ def predictor_fused(u, v, dx, dy, dt, nu_eff, use_supg=True, u_star=None, v_star
     if tau is None and use_supg:
         tau = torch.empty_like(u)
     nu_a, nu_s = _nu(nu_eff, u.dtype)
-    prev = None
-    if tau_mode is not None:
-        prev = int(lib().cfd_get_predictor2d_tau_mode())
-        if prev != TAU_MODES[tau_mode]:
-            call("cfd_set_predictor2d_tau_mode", TAU_MODES[tau_mode])
-        else:
-            prev = None
-    try:
-        call(_fields("cfd_predictor2d", u, v, us, vs, tau), ptr(u), ptr(v), ptr(nu_a), nu_s, ptr(us), ptr(vs),
-             ptr(tau), ny, nx, float(dx), float(dy), _dt_arg(dt, u.dtype), int(bool(use_supg)),
-             stream_handle())
-    finally:
-        if prev is not None:
-            call("cfd_set_predictor2d_tau_mode", prev)
+    _with_tau_mode(tau_mode, lambda: call(
+        _fields("cfd_predictor2d", u, v, us, vs, tau), ptr(u), ptr(v), ptr(nu_a), nu_s, ptr(us), ptr(vs),
+        ptr(tau), ny, nx, float(dx), float(dy), _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle()))
     return us, vs, tau
 
 

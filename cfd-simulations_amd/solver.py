@@ -8,11 +8,17 @@ names, method names and return values of
 v5.py:287).  Every
 per-step array pass runs in libcfdsim's gfx950 kernels, and the step needs no
 host synchronisation (except adaptive dt after step 1000, which, like the
-reference, reads max|V|).
+reference, reads max|V|, and with LES the mean nu_t in the same read).
 
-Out of scope: LES (``use_les=True`` raises,
-v5.py:60,381-384), plotting and video (OptimizedVisualizer), and HDF5 output
-(h5py is absent; ``save_snapshot`` writes the same layout to ``.npz``).
+LES (``use_les=True``, v5.py:60,96-110,381-388): the Smagorinsky eddy
+viscosity is formed inside the fused predictor (``K.predictor_fused_les``) and
+kept in ``nu_t``.  The reference ships with LES switched off and has no LES
+fixture, so this path is pinned to the project's own NumPy statement of the
+arithmetic (tests/les_reference.py); parity with the reference is unpinned.
+
+Out of scope: plotting and video (OptimizedVisualizer),
+and HDF5 output (h5py is absent; ``save_snapshot`` writes the same layout to
+``.npz``).
 """
 from __future__ import annotations
 
@@ -149,8 +155,6 @@ class OptimizedTurbulentSolver:
     """v5.py:259-441 on the GPU.  Array attributes are device tensors."""
 
     def __init__(self, config: OptimizedTurbulentConfig):
-        if config.use_les:
-            raise NotImplementedError("use_les=True is out of scope (LES is off in v3-v5, v5.py:60)")
         self.config = config
         # v5.py:287: float32 fields when memory_efficient, else float64
         self.dtype = torch.float32 if config.memory_efficient else torch.float64
@@ -196,6 +200,8 @@ class OptimizedTurbulentSolver:
         self._clean_ws = torch.empty(int(lib().cfd_clean_divergence_workspace_bytes(cfg.ny, cfg.nx)),
                                      dtype=torch.uint8, device=self.device)
         self._scal = torch.zeros(8, dtype=self.dtype, device=self.device)  # diagnostics
+        # LES adaptive dt: [mean nu_t (float64), max|V| (the fields' dtype, first bytes)]: one host read
+        self._dt_red = torch.zeros(2, dtype=torch.float64, device=self.device)
         self.initialize_potential_flow()
 
     def initialize_potential_flow(self):  # v5.py:299-314 (host, one-time)
@@ -210,13 +216,25 @@ class OptimizedTurbulentSolver:
             return cfg.dt_base
         if self.step < 1000:
             return np.float32(0.00002)
-        out = self._scal[0:1]
-        out.zero_()
-        call("cfd_absmax2" + self._sfx, ptr(self.u), ptr(self.v), self.u.numel(), ptr(out), stream_handle())
-        vmax = self._np(out.item())  # the one host read of the step (as in the reference)
+        if cfg.use_les:
+            # np.mean(nu_t) of the previous step's nu_t (v5.py:323) as a float64 device mean
+            # rounded to the fields' dtype, fetched with max|V| in the step's one host read
+            self._dt_red.zero_()
+            out = self._dt_red[1:2].view(self.dtype)[0:1]
+            call("cfd_absmax2" + self._sfx, ptr(self.u), ptr(self.v), self.u.numel(), ptr(out), stream_handle())
+            K.mean64(self.nu_t, out=self._dt_red[0:1])
+            red = self._dt_red.cpu().numpy()
+            vmax = red[1:2].view(self._np)[0]
+            nu_t_mean = self._np(red[0])
+        else:
+            out = self._scal[0:1]
+            out.zero_()
+            call("cfd_absmax2" + self._sfx, ptr(self.u), ptr(self.v), self.u.numel(), ptr(out), stream_handle())
+            vmax = self._np(out.item())  # the one host read of the step (as in the reference)
+            nu_t_mean = self._np(0.0)  # np.mean(nu_t) == 0 in the fields' dtype
         vel_max = max(vmax, 1e-10)
         dt_cfl = cfg.cfl_target * min(cfg.dx, cfg.dy) / vel_max
-        nu_total = cfg.nu + self._np(0.0) + cfg.artificial_viscosity  # np.mean(nu_t) == 0 in the fields' dtype
+        nu_total = cfg.nu + nu_t_mean + cfg.artificial_viscosity
         dt_visc = 0.4 * min(cfg.dx, cfg.dy) ** 2 / nu_total
         return np.float32(np.clip(min(dt_cfl, dt_visc), cfg.dt_min, cfg.dt_max))
 
@@ -313,11 +331,19 @@ class OptimizedTurbulentSolver:
         dt = self.adaptive_time_step()
         if diag:
             self._scal[1:5].zero_()
-        # predictor (v5.py:378-403): u_old/v_old are read-only here, so u/v are used directly;
-        # nu_eff = nu + nu_t + art_visc with nu_t == 0 in the fields' dtype (v5.py:388)
-        nu_eff = self._np(self._np(cfg.nu) + self._np(0.0)) + self._np(cfg.artificial_viscosity)
-        K.predictor_fused(self.u, self.v, cfg.dx, cfg.dy, dt, nu_eff, cfg.use_supg,
-                          u_star=self.u_star, v_star=self.v_star, tau=self.tau_supg, tau_mode=cfg.supg_tau)
+        # predictor (v5.py:378-403): u_old/v_old are read-only here, so u/v are used directly
+        if cfg.use_les:
+            # nu_t of u_old, v_old (v5.py:381-384) formed inside the predictor, kept in self.nu_t;
+            # nu_eff = (nu + nu_t) + art_visc per cell in the fields' dtype (v5.py:388)
+            K.predictor_fused_les(self.u, self.v, cfg.dx, cfg.dy, dt, self._np(cfg.nu),
+                                  self._np(cfg.artificial_viscosity), cfg.smagorinsky_constant, cfg.use_supg,
+                                  u_star=self.u_star, v_star=self.v_star, tau=self.tau_supg, nu_t=self.nu_t,
+                                  tau_mode=cfg.supg_tau)
+        else:
+            # nu_eff = nu + nu_t + art_visc with nu_t == 0 in the fields' dtype (v5.py:388)
+            nu_eff = self._np(self._np(cfg.nu) + self._np(0.0)) + self._np(cfg.artificial_viscosity)
+            K.predictor_fused(self.u, self.v, cfg.dx, cfg.dy, dt, nu_eff, cfg.use_supg,
+                              u_star=self.u_star, v_star=self.v_star, tau=self.tau_supg, tau_mode=cfg.supg_tau)
         # (without SUPG the predictor writes tau_supg's zeros itself)
         force_strength = min(1.0, self.step / cfg.initial_steps)
         # apply_boundary_conditions then apply_ibm_fast (v5.py:405-407), one launch
@@ -359,7 +385,8 @@ class OptimizedTurbulentSolver:
         .npz zip archive, so a save costs O(one group) however many the file
         holds, and a group already present is left alone without reading the
         device.  phi and the step counter are added (the reference stores
-        neither) so that load_snapshot restarts the run exactly."""
+        neither) so that load_snapshot restarts the run exactly; with LES so
+        is nu_t (the next adaptive dt reads the previous step's mean nu_t)."""
         import zipfile
         g = f"step_{step:06d}"
         exists = os.path.exists(path)
@@ -371,6 +398,8 @@ class OptimizedTurbulentSolver:
                   f"{g}/vorticity": self.compute_vorticity().cpu().numpy(),
                   f"{g}/X": self.X, f"{g}/Y": self.Y, f"{g}/phi": self.phi.cpu().numpy(),
                   f"{g}/time": np.float64(current_time), f"{g}/solver_step": np.int64(self.step)}
+        if self.config.use_les:
+            groups[f"{g}/nu_t"] = self.nu_t.cpu().numpy()
         with zipfile.ZipFile(path, "a" if exists else "w", compression=zipfile.ZIP_DEFLATED) as z:
             for k, arr in groups.items():
                 with z.open(f"{k}.npy", "w", force_zip64=True) as f:
@@ -395,6 +424,8 @@ class OptimizedTurbulentSolver:
             self.u.copy_(torch.from_numpy(f[f"{g}/u"]))
             self.v.copy_(torch.from_numpy(f[f"{g}/v"]))
             self.phi.copy_(torch.from_numpy(f[f"{g}/phi"]))
+            if self.config.use_les and f"{g}/nu_t" in f.files:
+                self.nu_t.copy_(torch.from_numpy(f[f"{g}/nu_t"]))
             self.step = int(f[f"{g}/solver_step"]) if f"{g}/solver_step" in f.files else int(g[5:])
             return float(f[f"{g}/time"])
 

@@ -190,6 +190,26 @@ int cfd_laplacian2d_f32(const float *phi, const float *nu_eff, float nu_eff_scal
 int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, float nu_eff_scalar,
                         float *u_star, float *v_star, float *tau, int ny, int nx,
                         double dx, double dy, float dt, int use_supg, void *stream);
+/* compute_smagorinsky_viscosity_fast, v5.py:96-110 (use_les=True): nu_t =
+ * (cs * sqrt(dx*dy))**2 * |S| on the interior, 0 on the boundary ring, |S| =
+ * sqrt(2 (dudx^2 + dvdy^2) + (dudy + dvdx)^2) from forward differences to the
+ * east and north neighbours, the square root correctly rounded; the constant
+ * is formed in Python floats (`**` = libm pow) and rounded once to the
+ * fields' type.  nu_t must not alias u or v. */
+int cfd_smagorinsky2d_f32(const float *u, const float *v, float *nu_t, int ny, int nx,
+                          double dx, double dy, double cs, void *stream);
+/* The fused predictor with LES (v5.py:381-403): cfd_smagorinsky2d's nu_t of
+ * u, v, then nu_eff = (nu + nu_t) + art_visc per cell feeding
+ * cfd_predictor2d's arithmetic -- the same bits as the two calls with a
+ * nu_eff array.  The row march forms nu_t from the rows it holds in registers
+ * (no extra reads) and stores it with tau; nu_t may then be NULL (not
+ * stored), like tau.  The one-thread-per-cell path (config variant 1, arrays
+ * past 2^31 bytes) runs the stand-alone nu_t kernel first and needs nu_t
+ * (CFD_E_INVALID without it).  cs = 0 gives cfd_predictor2d's bits with the
+ * scalar (nu + 0) + art_visc. */
+int cfd_predictor2d_les_f32(const float *u, const float *v, float nu, float art_visc, double cs,
+                            float *u_star, float *v_star, float *tau, float *nu_t, int ny, int nx,
+                            double dx, double dy, float dt, int use_supg, void *stream);
 /* Kernel of cfd_predictor2d_f32 / _f64 (tuning, per host thread; same bits
  * either way): variant 0 = auto (the row-march tile kernel when the arrays are
  * below 2^31 bytes; else one thread per cell), 1 = one thread per cell, 2 =
@@ -276,6 +296,10 @@ int cfd_energy_mean_clip2d_f32(float *u, float *v, size_t n, double *out, float 
 int cfd_absmax_f32(const float *a, size_t n, float *out, void *stream);            /* max|a| */
 int cfd_absmax2_f32(const float *a, const float *b, size_t n, float *out, void *stream);
 int cfd_energy_mean2d_f32(const float *u, const float *v, size_t n, double *out, void *stream);
+/* np.mean(a, dtype=float64) into a device double (adaptive dt's mean nu_t,
+ * v5.py:323): float64 partial sums in a fixed order, the same bits run to
+ * run; out need not be zeroed. */
+int cfd_mean_f32(const float *a, size_t n, double *out, void *stream);
 int cfd_vorticity_absmax2d_f32(const float *u, const float *v, const uint8_t *mask, int ny, int nx,
                                double dx, double dy, float *out, void *stream);
 /* compute_vorticity, v5.py:365-373 (masked cells NaN, boundary ring 0). */
@@ -310,6 +334,12 @@ int cfd_laplacian2d_f64(const double *phi, const double *nu_eff, double nu_eff_s
 int cfd_predictor2d_f64(const double *u, const double *v, const double *nu_eff, double nu_eff_scalar,
                         double *u_star, double *v_star, double *tau, int ny, int nx, double dx,
                         double dy, double dt, int use_supg, void *stream);
+/* cfd_smagorinsky2d_f32 / cfd_predictor2d_les_f32 on float64 fields */
+int cfd_smagorinsky2d_f64(const double *u, const double *v, double *nu_t, int ny, int nx,
+                          double dx, double dy, double cs, void *stream);
+int cfd_predictor2d_les_f64(const double *u, const double *v, double nu, double art_visc, double cs,
+                            double *u_star, double *v_star, double *tau, double *nu_t, int ny, int nx,
+                            double dx, double dy, double dt, int use_supg, void *stream);
 int cfd_divergence2d_f64(const double *u, const double *v, double *div, int ny, int nx, double dx,
                          double dy, double *absmax, void *stream);
 int cfd_gradient2d_f64(const double *phi, double *grad_x, double *grad_y, int ny, int nx, double dx,
@@ -332,6 +362,7 @@ int cfd_numpy_pow_f64(const double *x, double y, double *out, size_t n, void *st
 /* max(|a|, |b|) (b may be NULL) into a zeroed device double */
 int cfd_absmax2_f64(const double *a, const double *b, size_t n, double *out, void *stream);
 int cfd_energy_mean2d_f64(const double *u, const double *v, size_t n, double *out, void *stream);
+int cfd_mean_f64(const double *a, size_t n, double *out, void *stream);
 int cfd_apply_bc_ibm2d_f64(double *u, double *v, const double *y, int ny, int nx, double y_max,
                            double v_inf, int step, const double *ibm_mask, double force_strength,
                            void *stream);
@@ -589,7 +620,7 @@ int cfd_get_last_tbr_shape(int *levels, int *row_waves, int *rows_per_wave, int 
 int cfd_timing_enable(int enable);
 int cfd_timing_read(double *ms, long long *sweeps, int reset);
 /* The same for one channel: 0 = the pressure solves (cfd_timing_read), 1 =
- * the predictor launches (cfd_predictor2d_f32 / _f64, one count per launch),
+ * the predictor launches (cfd_predictor2d_f32 / _f64 / _les_*, one count per launch),
  * so a timed time_step reports the solve's sweeps without the predictor in
  * them.  reset clears the channel read (the other channel's timings stay). */
 int cfd_timing_read_channel(int channel, double *ms, long long *sweeps, int reset);
