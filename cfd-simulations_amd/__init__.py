@@ -7,7 +7,8 @@ Layers:
                built into libcfdsim.so in this directory
   _lib.py      ctypes binding of that ABI (no fallback if the library is absent)
   kernels.py   reference-named kernel functions (the @njit drop-ins)
-  solver.py    OptimizedTurbulentConfig / OptimizedTurbulentSolver drop-ins
+  solver.py    OptimizedTurbulentConfig / OptimizedTurbulentSolver drop-ins, the
+               2-D and 3-D lid-driven cavity solvers
   slab.py      multi-GPU slab decomposition with RCCL halo exchange
 
 Importing the package does not load the HIP library; the first kernel call
@@ -18,6 +19,7 @@ from __future__ import annotations
 __version__ = "0.1.0"
 
 from .solver import (OptimizedTurbulentConfig, OptimizedTurbulentSolver,  # noqa: F401
-                     monitor_simulation_health, host_grid, host_masks, host_potential_flow)
+                     monitor_simulation_health, host_grid, host_masks, host_potential_flow,
+                     LidDrivenCavity3DConfig, LidDrivenCavity3DSolver, monitor_simulation_health3d)
 from .slab import SlabPlan  # noqa: F401
 from . import kernels  # noqa: F401

@@ -85,6 +85,15 @@ PROTOTYPES = {
     "cfd_vorticity2d_f32": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_nonfinite_count_f32": (c_int, [P, P, c_size_t, P, P]),
     "cfd_numpy_powf_f32": (c_int, [P, c_float, P, c_size_t, P]),
+    "cfd_predictor3d_f32": (c_int, [P, P, P, c_float, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
+                                    c_double, c_float, c_int, P]),
+    "cfd_set_predictor3d_config": (c_int, [c_int, c_int, c_int]),
+    "cfd_get_last_predictor3d_path": (c_int, [ctypes.POINTER(c_int)]),
+    "cfd_divergence3d_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
+    "cfd_project3d_f32": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
+                                  c_float, P, P]),
+    "cfd_apply_lid_bc3d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
+    "cfd_energy_mean_clip3d_f32": (c_int, [P, P, P, c_size_t, P, c_float, c_float, P]),
     "cfd_supg_tau2d_f64": (c_int, [P, P, P, c_double, P, c_int, c_int, c_double, c_double, c_double, P]),
     "cfd_convection_supg2d_f64": (c_int, [P, P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_convection_upwind2d_f64": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),

@@ -1,0 +1,378 @@
+// fields3d.hip -- the 3-D projection step around the 3-D pressure solves, for
+// gfx950: fused advection-diffusion predictor, divergence, gradient +
+// projection, lid-driven cavity walls and the energy / clip epilogue on
+// (nz, ny, nx) float32 fields u, v, w (x fastest; E/W = x+-1, N/S = y+-1,
+// U/D = z+-1).
+//
+// The arithmetic is the project's own 3-D generalisation of the v5 templates
+// (fields2d.hip), every 2-D coefficient kept and a z term appended to each
+// sum; tests/ref3d.py states it as NumPy array code and the kernels reproduce
+// it bit for bit (float32 operations in the source order, nothing fused).
+// All indexing is 64-bit.
+#include <map>
+#include <mutex>
+
+#include "common.hpp"
+#include "internal.hpp"
+#include "pred_planes.hpp"
+
+namespace cfd {
+
+__device__ inline bool interior3(int k, int j, int i, int nz, int ny, int nx) {
+    return k >= 1 && k < nz - 1 && j >= 1 && j < ny - 1 && i >= 1 && i < nx - 1;
+}
+
+// one thread per cell: blockIdx.y = row, blockIdx.z = plane
+#define CFD_3D_INDEX                                     \
+    const int i = blockIdx.x * blockDim.x + threadIdx.x; \
+    const int j = blockIdx.y;                            \
+    const int k = blockIdx.z;                            \
+    const bool cell = i < nx;                            \
+    const size_t sy = (size_t)nx, sz = (size_t)ny * nx;  \
+    const size_t c = ((size_t)k * ny + j) * nx + (cell ? i : 0);
+
+// The fused predictor, one thread per cell (plain loads; the neighbours come
+// from L1 / L2): the fallback of the plane march for unaligned shapes and its
+// yardstick.  pred3_tau / pred3_cell: pred_planes.hpp.
+template <bool SUPG>
+__global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u, const float *__restrict__ v,
+                                                     const float *__restrict__ w, float nu,
+                                                     float *__restrict__ us, float *__restrict__ vs,
+                                                     float *__restrict__ ws, float *__restrict__ tau_out, int nz,
+                                                     int ny, int nx, float dt, PredK3 kk) {
+    CFD_3D_INDEX
+    if (!cell) return;
+    const float uc = u[c], vc = v[c], wc = w[c];
+    float uo = uc, vo = vc, wo = wc, t = 0.0f;  // the six faces keep f (tau: 0)
+    if (interior3(k, j, i, nz, ny, nx)) {
+        const Nb7 fu = {uc, u[c + 1], u[c - 1], u[c + sy], u[c - sy], u[c + sz], u[c - sz]};
+        const Nb7 fv = {vc, v[c + 1], v[c - 1], v[c + sy], v[c - sy], v[c + sz], v[c - sz]};
+        const Nb7 fw = {wc, w[c + 1], w[c - 1], w[c + sy], w[c - sy], w[c + sz], w[c - sz]};
+        if (SUPG) t = pred3_tau(uc, vc, wc, nu, dt, kk);
+        uo = pred3_cell<SUPG>(uc, vc, wc, fu, t, nu, dt, kk);
+        vo = pred3_cell<SUPG>(uc, vc, wc, fv, t, nu, dt, kk);
+        wo = pred3_cell<SUPG>(uc, vc, wc, fw, t, nu, dt, kk);
+    }
+    us[c] = uo;
+    vs[c] = vo;
+    ws[c] = wo;
+    if (tau_out) tau_out[c] = t;  // zeros without SUPG
+}
+
+// ((uE - uW) cx + (vN - vS) cy) + (wU - wD) cz, 0 on the six faces (+ max|div|)
+__global__ __launch_bounds__(256) void k_divergence3d(const float *__restrict__ u, const float *__restrict__ v,
+                                                      const float *__restrict__ w, float *__restrict__ div, int nz,
+                                                      int ny, int nx, float cx, float cy, float cz, float *absmax) {
+    CFD_3D_INDEX
+    float m = 0.0f;
+    if (cell) {
+        float d = 0.0f;
+        if (interior3(k, j, i, nz, ny, nx))
+            d = ((u[c + 1] - u[c - 1]) * cx + (v[c + sy] - v[c - sy]) * cy) + (w[c + sz] - w[c - sz]) * cz;
+        div[c] = d;
+        const float a = fabsf(d);
+        if (a > m) m = a;
+    }
+    if (absmax) wave_reduce_max_store(m, absmax);
+}
+
+// gradient of phi (0 on the faces), u = u* - dt gx, v = v* - dt gy,
+// w = w* - dt gz; gradmax <- max sqrt((gx^2 + gy^2) + gz^2)
+__global__ __launch_bounds__(256) void k_project3d(const float *__restrict__ phi, const float *__restrict__ us,
+                                                   const float *__restrict__ vs, const float *__restrict__ ws,
+                                                   float *__restrict__ u, float *__restrict__ v,
+                                                   float *__restrict__ w, int nz, int ny, int nx, float cx, float cy,
+                                                   float cz, float dt, float *gradmax) {
+    CFD_3D_INDEX
+    float m = 0.0f;
+    if (cell) {
+        float uo = us[c], vo = vs[c], wo = ws[c];  // the faces copy u* through
+        if (interior3(k, j, i, nz, ny, nx)) {
+            const float gx = (phi[c + 1] - phi[c - 1]) * cx;
+            const float gy = (phi[c + sy] - phi[c - sy]) * cy;
+            const float gz = (phi[c + sz] - phi[c - sz]) * cz;
+            uo = uo - dt * gx;
+            vo = vo - dt * gy;
+            wo = wo - dt * gz;
+            if (gradmax) {
+                const float g = sqrtf((gx * gx + gy * gy) + gz * gz);
+                if (g > m) m = g;
+            }
+        }
+        u[c] = uo;
+        v[c] = vo;
+        w[c] = wo;
+    }
+    if (gradmax) wave_reduce_max_store(m, gradmax);
+}
+
+// Lid-driven cavity walls in 3-D (host_lid_bc's pattern): u = v = w = 0 on the
+// six faces, then the face y = ny - 1 gets u = u_lid, v = w = 0; the lid is
+// written last, so it owns its edges.  One thread per cell of the largest
+// face; a cell on an edge is written by the threads of both its faces with
+// the same value (u_lid on row ny - 1, else 0).
+__global__ void k_lid_bc3d(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w, int nz, int ny,
+                           int nx, float u_lid) {
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t sy = (size_t)nx, sz = (size_t)ny * nx;
+    auto put = [&](size_t c, bool lid) {
+        u[c] = lid ? u_lid : 0.0f;
+        v[c] = 0.0f;
+        w[c] = 0.0f;
+    };
+    if (t < sz) {  // planes z = 0 and z = nz - 1
+        const bool lid = t / sy == (size_t)(ny - 1);
+        put(t, lid);
+        put((size_t)(nz - 1) * sz + t, lid);
+    }
+    if (t < (size_t)nz * nx) {  // rows y = 0 and y = ny - 1 (the lid)
+        const size_t k = t / nx, i = t % nx;
+        put(k * sz + i, false);
+        put(k * sz + (size_t)(ny - 1) * sy + i, true);
+    }
+    if (t < (size_t)nz * ny) {  // columns x = 0 and x = nx - 1
+        const size_t k = t / ny, j = t % ny;
+        const bool lid = j == (size_t)(ny - 1);
+        put(k * sz + j * sy, lid);
+        put(k * sz + j * sy + (nx - 1), lid);
+    }
+}
+
+// Mean of 0.5 ((u*u + v*v) + w*w) over n cells, then the three clips, in one
+// launch: k_energy_mean_mb's scheme (block b folds a fixed contiguous range
+// thread-strided into float64 partials, the last block to take a ticket adds
+// the block partials in block order: the same bits run to run) on three
+// fields and up to kEnergy3Blocks blocks.  Each cell's energy is formed in
+// float32 from the values loaded (before the clip).  The partials and the
+// ticket live in a slot of static device memory (no allocation): one slot per
+// (device, stream), handed out on the host.
+constexpr int kEnergy3Blocks = 512;
+constexpr int kEnergy3Slots = 32;
+struct Energy3Slot {
+    unsigned ticket;  // zero between calls (the last block resets it)
+    double partial[kEnergy3Blocks];
+};
+__device__ Energy3Slot g_energy3[kEnergy3Slots];
+
+__global__ __launch_bounds__(256) void k_energy_mean_clip3d(float *__restrict__ u, float *__restrict__ v,
+                                                            float *__restrict__ w, size_t n, double *out, float lo,
+                                                            float hi, int slot) {
+    constexpr int U = 4;
+    __shared__ double part[4];
+    __shared__ int last;
+    __shared__ double all[kEnergy3Blocks];
+    Energy3Slot &ws = g_energy3[slot];
+    const size_t per = (n + gridDim.x - 1) / gridDim.x;
+    const size_t b0 = blockIdx.x * per < n ? blockIdx.x * per : n, b1 = b0 + per < n ? b0 + per : n;
+    double s[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) s[q] = 0.0;
+    auto cell = [&](size_t c, double &acc) {
+        const float a = u[c], b = v[c], d = w[c];
+        acc += (double)(0.5f * ((a * a + b * b) + d * d));
+        u[c] = clip_val(a, lo, hi);
+        v[c] = clip_val(b, lo, hi);
+        w[c] = clip_val(d, lo, hi);
+    };
+    size_t c = b0 + threadIdx.x;
+    for (; c + (U - 1) * 256 < b1; c += U * 256) {
+#pragma unroll
+        for (int q = 0; q < U; ++q) cell(c + q * 256, s[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q)
+        if (c + q * 256 < b1) cell(c + q * 256, s[q]);
+    double t = s[0];
+#pragma unroll
+    for (int q = 1; q < U; ++q) t += s[q];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, kWave);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws.partial[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+        __threadfence();  // the partial before the ticket
+        last = atomicAdd(&ws.ticket, 1u) == (unsigned)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    for (int q = threadIdx.x; q < (int)gridDim.x; q += blockDim.x)
+        all[q] = __hip_atomic_load(&ws.partial[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = 0.0;
+        for (int q = 0; q < (int)gridDim.x; ++q) r += all[q];
+        *out = r * (1.0 / (double)n);
+        __hip_atomic_store(&ws.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// the (device, stream)'s slot of g_energy3, or -1 when all are taken
+static int energy3_slot(hipStream_t s) {
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, int> slots;
+    static int used[64] = {};  // per device
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = slots.find({dev, s});
+    if (it != slots.end()) return it->second;
+    if (used[dev] >= kEnergy3Slots) return -1;
+    return slots[{dev, s}] = used[dev]++;
+}
+
+static dim3 grid3d(int nz, int ny, int nx) { return dim3(ceil_div(nx, 256), ny, nz); }
+
+static thread_local int g_last_pred3[2] = {-1, 0};
+
+}  // namespace cfd
+
+using namespace cfd;
+
+// every dimension >= 3 (one interior cell), rows and planes within a launch grid
+#define CFD_SHAPE3D(who, nz, ny, nx)                                                                        \
+    CFD_REQUIRE((nz) >= 3 && (ny) >= 3 && (nx) >= 3 && (ny) <= 65535 && (nz) <= 65535,                       \
+                "%s: bad 3-D shape (%d, %d, %d): every dimension 3 .. 65535 (nx: any >= 3)", who, nz, ny, nx)
+
+extern "C" {
+
+int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
+                        float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
+                        double dz, float dt, int use_supg, void *stream) {
+    CFD_REQUIRE(u && v && w && u_star && v_star && w_star, "predictor3d: null pointer");
+    CFD_SHAPE3D("predictor3d", nz, ny, nx);
+    const float *in[3] = {u, v, w};
+    float *out[4] = {u_star, v_star, w_star, tau};
+    for (int o = 0; o < 4; ++o) {
+        for (int q = 0; q < 3; ++q)
+            CFD_REQUIRE(out[o] != in[q], "predictor3d: outputs must not alias inputs");
+        for (int p = 0; p < o; ++p)
+            CFD_REQUIRE(!out[o] || out[o] != out[p], "predictor3d: outputs must not alias each other");
+    }
+    const PredK3 k = make_pred_k3(dx, dy, dz);
+    hipStream_t s = as_stream(stream);
+    // cells per lane of the plane march: the preferred count (tuning; auto: 4,
+    // 2 where a 256-column segment would be wider than the grid), halved until
+    // nx and every array's alignment allow it (1 always does)
+    int vec = tuning().pred3_vec;
+    if (!vec) vec = nx < 256 ? 2 : 4;
+    auto fits = [&](int c) {
+        const uintptr_t m = (uintptr_t)(4 * c - 1);
+        auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
+        return nx % c == 0 && al(u) && al(v) && al(w) && al(u_star) && al(v_star) && al(w_star) && al(tau);
+    };
+    while (vec > 1 && !fits(vec)) vec /= 2;
+    // the march runs where a plane's byte offsets fit its buffer resource and
+    // (auto) nx and the alignment leave it more than one cell per lane; a
+    // forced march (variant 2) also runs at one
+    const bool plane_ok = (size_t)ny * nx * sizeof(float) < ((size_t)1 << 31);
+    const int variant = tuning().pred3_variant;
+    const bool march = plane_ok && variant != 1 && (variant == 2 || vec > 1);
+    const int tk = timing_begin(s, kTimingPredictor);
+    if (march) {
+        Pred3Args a;
+        a.u = u;
+        a.v = v;
+        a.w = w;
+        a.us = u_star;
+        a.vs = v_star;
+        a.ws = w_star;
+        a.tau = tau;
+        a.nu = nu_eff;
+        a.dt = dt;
+        a.nz = nz;
+        a.ny = ny;
+        a.nx = nx;
+        a.k = k;
+        const int rows = tuning().pred3_rows ? tuning().pred3_rows : 2;
+        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, vec, rows, 0, s));
+        g_last_pred3[0] = 1;
+        g_last_pred3[1] = vec;
+    } else {
+        if (use_supg)
+            hipLaunchKernelGGL(k_predictor3d<true>, grid3d(nz, ny, nx), dim3(256), 0, s, u, v, w, nu_eff, u_star,
+                               v_star, w_star, tau, nz, ny, nx, dt, k);
+        else
+            hipLaunchKernelGGL(k_predictor3d<false>, grid3d(nz, ny, nx), dim3(256), 0, s, u, v, w, nu_eff, u_star,
+                               v_star, w_star, tau, nz, ny, nx, dt, k);
+        g_last_pred3[0] = 0;
+        g_last_pred3[1] = 1;
+    }
+    timing_end(tk, s, 1);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_set_predictor3d_config(int variant, int rows, int cells_per_lane) {
+    CFD_REQUIRE(variant >= 0 && variant <= 2, "predictor3d config: variant 0 (auto), 1 (per cell) or 2 (plane march)");
+    CFD_REQUIRE(rows == 0 || rows == 1 || rows == 2, "predictor3d config: rows per wave 0 (auto), 1 or 2");
+    CFD_REQUIRE(cells_per_lane == 0 || cells_per_lane == 1 || cells_per_lane == 2 || cells_per_lane == 4,
+                "predictor3d config: cells per lane 0 (auto), 1, 2 or 4");
+    tuning().pred3_variant = variant;
+    tuning().pred3_rows = rows;
+    tuning().pred3_vec = cells_per_lane;
+    return CFD_OK;
+}
+
+int cfd_get_last_predictor3d_path(int *cells_per_lane) {
+    if (cells_per_lane) *cells_per_lane = g_last_pred3[1];
+    return g_last_pred3[0];
+}
+
+int cfd_divergence3d_f32(const float *u, const float *v, const float *w, float *div, int nz, int ny, int nx,
+                         double dx, double dy, double dz, float *absmax, void *stream) {
+    CFD_REQUIRE(u && v && w && div, "divergence3d: null pointer");
+    CFD_REQUIRE(div != u && div != v && div != w, "divergence3d: div must not alias an input");
+    CFD_SHAPE3D("divergence3d", nz, ny, nx);
+    hipLaunchKernelGGL(k_divergence3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, div, nz, ny, nx,
+                       (float)(0.5 / dx), (float)(0.5 / dy), (float)(0.5 / dz), absmax);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_project3d_f32(const float *phi, const float *u_star, const float *v_star, const float *w_star, float *u,
+                      float *v, float *w, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                      float *gradmax, void *stream) {
+    CFD_REQUIRE(phi && u_star && v_star && w_star && u && v && w, "project3d: null pointer");
+    const float *in[4] = {phi, u_star, v_star, w_star};
+    float *out[3] = {u, v, w};
+    for (int o = 0; o < 3; ++o) {
+        for (int q = 0; q < 4; ++q) CFD_REQUIRE(out[o] != in[q], "project3d: outputs must not alias inputs");
+        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "project3d: outputs must not alias each other");
+    }
+    CFD_SHAPE3D("project3d", nz, ny, nx);
+    hipLaunchKernelGGL(k_project3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), phi, u_star, v_star, w_star,
+                       u, v, w, nz, ny, nx, (float)(0.5 / dx), (float)(0.5 / dy), (float)(0.5 / dz), dt, gradmax);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_apply_lid_bc3d_f32(float *u, float *v, float *w, int nz, int ny, int nx, float u_lid, void *stream) {
+    CFD_REQUIRE(u && v && w, "apply_lid_bc3d: null pointer");
+    CFD_REQUIRE(u != v && u != w && v != w, "apply_lid_bc3d: u, v, w must be three arrays");
+    CFD_SHAPE3D("apply_lid_bc3d", nz, ny, nx);
+    size_t n = (size_t)ny * nx;
+    if ((size_t)nz * nx > n) n = (size_t)nz * nx;
+    if ((size_t)nz * ny > n) n = (size_t)nz * ny;
+    hipLaunchKernelGGL(k_lid_bc3d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), u, v, w, nz,
+                       ny, nx, u_lid);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *out, float lo, float hi,
+                               void *stream) {
+    CFD_REQUIRE(u && v && w && out && n > 0, "energy_mean_clip3d_f32: bad arguments");
+    CFD_REQUIRE(u != v && u != w && v != w, "energy_mean_clip3d_f32: u, v, w must be three arrays");
+    hipStream_t s = as_stream(stream);
+    const int slot = energy3_slot(s);
+    CFD_REQUIRE(slot >= 0, "energy_mean_clip3d_f32: more than %d streams of one device in use", kEnergy3Slots);
+    size_t nb = (n + 4095) / 4096;  // ~16 cells per thread
+    if (nb > (size_t)kEnergy3Blocks) nb = kEnergy3Blocks;
+    hipLaunchKernelGGL(k_energy_mean_clip3d, dim3((unsigned)nb), dim3(256), 0, s, u, v, w, n, out, lo, hi, slot);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+}  // extern "C"

@@ -64,6 +64,12 @@ struct Tuning {
     // NumPy scalars), 1 fast (x*x, correctly rounded sqrt, rcp + Newton
     // divisions: the compiled reference's fastmath arithmetic, within 1e-6)
     int pred_tau = 0;
+    // fused 3-D predictor (cfd_predictor3d_f32): 0 auto (the plane march where
+    // nx and the alignment give it 2 or 4 cells per lane), 1 one thread per
+    // cell, 2 plane march; rows per wave of the march (0: 2; 1, 2); preferred
+    // cells per lane (0: 4, 2 below 256 columns; 1, 2, 4), halved until nx
+    // and every pointer's alignment fit
+    int pred3_variant = 0, pred3_rows = 0, pred3_vec = 0;
     // persistent small-grid solves (jacobi2d_persist, rbgs2d_persist): 0 = a
     // plain launch after the occupancy check (r05 default: the cooperative
     // launch cost ~30 us of queue gap per solve, 0.79 -> 0.76 ms per v5

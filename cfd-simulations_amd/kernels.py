@@ -24,6 +24,7 @@ __all__ = [
     "compute_smagorinsky_viscosity_fast", "predictor_fused_les", "mean64",
     "solve_pressure_jacobi3d_zero",
     "solve_pressure_gauss_seidel3d", "persistent_failures",
+    "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
 ]
 
 
@@ -388,6 +389,79 @@ def project_velocity(phi, u_star, v_star, dx, dy, dt, u=None, v=None, gradmax=No
     call(_fields("cfd_project2d", phi, u_star, v_star, u, v, gradmax), ptr(phi), ptr(u_star), ptr(v_star), ptr(u),
          ptr(v), ny, nx, float(dx), float(dy), _dt_arg(dt, phi.dtype), ptr(gradmax), stream_handle())
     return u, v
+
+
+# ------------------------------------------------------ 3-D projection step
+def _shape3d(t: torch.Tensor):
+    if t.dim() != 3:
+        raise ValueError(f"expected a 3-D (nz, ny, nx) array, got shape {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+
+
+def _fields3d(model, /, **others):
+    """model as the (nz, ny, nx) float32 pattern; every other array (None
+    passes) must match its shape, dtype, device and be C-contiguous."""
+    shape = _shape3d(_f32(model, "field"))
+    ptr(model)  # device and contiguity
+    for name, t in others.items():
+        _like(model, t, name)
+    return shape
+
+
+def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=None, v_star=None, w_star=None,
+                      tau=None, store_tau=True):
+    """The 3-D fused predictor (cfd_predictor3d_f32): SUPG tau, convection and
+    Laplacian of u, v, w and f_star = f + dt*(-conv + lap) in one pass, the six
+    faces copied through.  ``nu_eff`` is a scalar.  Returns (u_star, v_star,
+    w_star, tau); arrays not given are allocated.  ``store_tau=False`` with no
+    ``tau`` given: tau is not stored (24 B per cell instead of 28) and None is
+    returned for it.  Without SUPG a stored tau is zeros."""
+    us = torch.empty_like(u) if u_star is None else u_star
+    vs = torch.empty_like(u) if v_star is None else v_star
+    ws = torch.empty_like(u) if w_star is None else w_star
+    if tau is None and store_tau:
+        tau = torch.empty_like(u)
+    nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau)
+    call("cfd_predictor3d_f32", ptr(u), ptr(v), ptr(w), float(np.float32(nu_eff)), ptr(us), ptr(vs), ptr(ws),
+         ptr(tau), nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)),
+         stream_handle())
+    return us, vs, ws, tau
+
+
+def compute_divergence3d(u, v, w, dx, dy, dz, out=None, absmax=None):
+    """div = ((uE-uW) cx + (vN-vS) cy) + (wU-wD) cz, 0 on the six faces.
+    ``absmax``: optional zeroed float32 device scalar that receives max|div|
+    without a host sync.  Returns div (``out`` if given)."""
+    div = torch.empty_like(u) if out is None else out
+    nz, ny, nx = _fields3d(u, v=v, w=w, div=div)
+    if absmax is not None:
+        _f32(absmax, "absmax")
+    call("cfd_divergence3d_f32", ptr(u), ptr(v), ptr(w), ptr(div), nz, ny, nx, float(dx), float(dy), float(dz),
+         ptr(absmax), stream_handle())
+    return div
+
+
+def project_velocity3d(phi, u_star, v_star, w_star, dx, dy, dz, dt, u=None, v=None, w=None, gradmax=None):
+    """u = u* - dt dphi/dx, v = v* - dt dphi/dy, w = w* - dt dphi/dz on the
+    interior, the faces copied through.  ``gradmax``: optional zeroed float32
+    device scalar for max|grad phi|.  Returns (u, v, w)."""
+    u = torch.empty_like(phi) if u is None else u
+    v = torch.empty_like(phi) if v is None else v
+    w = torch.empty_like(phi) if w is None else w
+    nz, ny, nx = _fields3d(phi, u_star=u_star, v_star=v_star, w_star=w_star, u=u, v=v, w=w)
+    if gradmax is not None:
+        _f32(gradmax, "gradmax")
+    call("cfd_project3d_f32", ptr(phi), ptr(u_star), ptr(v_star), ptr(w_star), ptr(u), ptr(v), ptr(w), nz, ny, nx,
+         float(dx), float(dy), float(dz), _dt_arg(dt, phi.dtype), ptr(gradmax), stream_handle())
+    return u, v, w
+
+
+def apply_lid_bc3d(u, v, w, u_lid):
+    """Cavity walls in place: u = v = w = 0 on the six faces, then u = u_lid,
+    v = w = 0 on the face y = ny - 1 (the lid owns its edges).  Returns (u, v, w)."""
+    nz, ny, nx = _fields3d(u, v=v, w=w)
+    call("cfd_apply_lid_bc3d_f32", ptr(u), ptr(v), ptr(w), nz, ny, nx, float(np.float32(u_lid)), stream_handle())
+    return u, v, w
 
 
 def persistent_failures(stream=None) -> int:

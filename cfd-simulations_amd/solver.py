@@ -16,6 +16,9 @@ kept in ``nu_t``.  The reference ships with LES switched off and has no LES
 fixture, so this path is pinned to the project's own NumPy statement of the
 arithmetic (tests/les_reference.py); parity with the reference is unpinned.
 
+``LidDrivenCavity3DSolver`` is the same projection step in 3-D around the 3-D
+pressure solves (the project's own generalisation: the reference is 2-D only).
+
 Out of scope: plotting and video (OptimizedVisualizer),
 and HDF5 output (h5py is absent; ``save_snapshot`` writes the same layout to
 ``.npz``).
@@ -493,6 +496,194 @@ class LidDrivenCavitySolver(OptimizedTurbulentSolver):
     def apply_boundary_conditions(self, u, v):
         call("cfd_apply_lid_bc2d" + self._sfx, ptr(u), ptr(v), self.config.ny, self.config.nx,
              float(self._np(self.config.lid_velocity)), stream_handle())
+
+
+# --------------------------------------------------- 3-D lid-driven cavity
+@dataclass
+class LidDrivenCavity3DConfig(OptimizedTurbulentConfig):
+    """The lid-driven cavity in 3-D: the v5 fields plus nz, z_min, z_max and
+    the derived dz.  128^3 on the unit cube, Re = 100, artificial viscosity
+    1e-3, 200 Jacobi iterations per pressure solve (use_fast_pressure=False;
+    True selects the 3-D red-black GS), the lid y = y_max moving at
+    lid_velocity in x."""
+    x_max: float = 1.0
+    y_max: float = 1.0
+    z_min: float = 0.0
+    z_max: float = 1.0
+    nx: int = 128
+    ny: int = 128
+    nz: int = 128
+    Re: float = 100.0
+    artificial_viscosity: float = 0.001
+    pressure_iterations: int = 200
+    use_fast_pressure: bool = False
+    lid_velocity: float = 1.0
+    output_dir: str = "cavity3d_re_100"
+    hdf5_file: str = "cavity3d_re_100.h5"
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.dz = (self.z_max - self.z_min) / (self.nz - 1)
+        if self.use_les:
+            raise ValueError("LidDrivenCavity3DConfig: LES is 2-D only")
+        if not self.memory_efficient:
+            raise ValueError("LidDrivenCavity3DConfig: the 3-D step is float32 only (memory_efficient=True)")
+
+
+class LidDrivenCavity3DSolver:
+    """The projection step around the 3-D pressure solves on one GPU: the
+    project's own 3-D generalisation of the v5 time step (every 2-D
+    coefficient kept, a z term appended; tests/ref3d.py states the arithmetic)
+    on the lid-driven cavity, fields (nz, ny, nx) float32 device tensors.
+
+    time_step: dt, fused predictor (K.predictor3d_fused, tau not stored), lid
+    walls, divergence, pressure solve (phi from zeros: cfd_jacobi3d_zero_f32,
+    or cfd_rbgs3d_f32 with use_fast_pressure), projection, lid walls, mean
+    kinetic energy and the three clips.  No host synchronisation, except the
+    adaptive dt's one read of max|V| from step 1000 on.
+
+    Out of scope: snapshots, LES, immersed boundaries or masks, float64, a
+    slab-decomposed (multi-GPU) step, and the 2-D step's clean_divergence
+    stage (a v5 quirk with serial semantics that does not generalise)."""
+
+    def __init__(self, config: LidDrivenCavity3DConfig):
+        self.config = cfg = config
+        self.dtype = torch.float32
+        self.device = torch.device(cfg.device)
+        if self.device.type != "cuda":
+            raise TypeError("LidDrivenCavity3DSolver runs on the HIP device only")
+        shape = (cfg.nz, cfg.ny, cfg.nx)
+        z = lambda: torch.zeros(shape, dtype=self.dtype, device=self.device)  # noqa: E731
+        self.u, self.v, self.w = z(), z(), z()  # fluid at rest
+        self.u_star, self.v_star, self.w_star = z(), z(), z()
+        self.div_u_star, self.phi = z(), z()
+        self._phi_tmp, self._rhs_ws = z(), z()
+        self._gs_ws = torch.empty(int(lib().cfd_rbgs_workspace_bytes(cfg.pressure_iterations)), dtype=torch.uint8,
+                                  device=self.device)
+        self._gs_done = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._scal = torch.zeros(4, dtype=self.dtype, device=self.device)  # [max|V|, pre_div_max, grad_max]
+        self._energy = torch.zeros(1024, dtype=torch.float64, device=self.device)
+        self._energy_steps = []
+        self.times = []
+        self.step = 0
+
+    def adaptive_time_step(self):
+        """The v5 rule (v5.py:316-326) with max(|u|, |v|, |w|) and min(dx, dy, dz)."""
+        cfg = self.config
+        if not cfg.adaptive_dt:
+            return cfg.dt_base
+        if self.step < 1000:
+            return np.float32(0.00002)
+        s = stream_handle()
+        out = self._scal[0:1]
+        out.zero_()
+        n = self.u.numel()
+        call("cfd_absmax2_f32", ptr(self.u), ptr(self.v), n, ptr(out), s)
+        call("cfd_absmax_f32", ptr(self.w), n, ptr(out), s)  # the max accumulates
+        vel_max = max(np.float32(out.item()), 1e-10)  # the one host read of the step
+        h = min(cfg.dx, cfg.dy, cfg.dz)
+        dt_cfl = cfg.cfl_target * h / vel_max
+        nu_total = cfg.nu + np.float32(0.0) + cfg.artificial_viscosity
+        dt_visc = 0.4 * h ** 2 / nu_total
+        return np.float32(np.clip(min(dt_cfl, dt_visc), cfg.dt_min, cfg.dt_max))
+
+    def solve_pressure_fast(self, div_u_star):
+        """phi = zeros, then the solve (with cfg.dt, like v5.py:328-347):
+        red-black GS on any spacing (use_fast_pressure), else the 7-point
+        Jacobi, which needs dx == dy == dz exactly."""
+        cfg = self.config
+        if cfg.use_fast_pressure:
+            self.phi.zero_()
+            K.solve_pressure_gauss_seidel3d(self.phi, div_u_star, cfg.dx, cfg.dy, cfg.dz, cfg.dt, None,
+                                            cfg.pressure_iterations, cfg.pressure_tolerance, workspace=self._gs_ws,
+                                            iters_done=self._gs_done, phi_tmp=self._phi_tmp)
+        else:
+            if not (cfg.dx == cfg.dy == cfg.dz):
+                raise ValueError(f"the 3-D Jacobi solve needs dx == dy == dz (got {cfg.dx}, {cfg.dy}, {cfg.dz}); "
+                                 "use_fast_pressure=True takes any spacing")
+            K.solve_pressure_jacobi3d_zero(self.phi, div_u_star, cfg.dx, cfg.dt, cfg.pressure_iterations,
+                                           phi_tmp=self._phi_tmp, rhs_ws=self._rhs_ws)
+        return self.phi
+
+    def apply_boundary_conditions(self, u, v, w):
+        K.apply_lid_bc3d(u, v, w, self.config.lid_velocity)
+
+    @property
+    def energy_history(self):
+        """[(step, mean kinetic energy)], read lazily from the device."""
+        n = len(self._energy_steps)
+        vals = self._energy[:n].cpu().numpy() if n else np.zeros(0)
+        return [(s, float(e)) for s, e in zip(self._energy_steps, vals)]
+
+    @property
+    def diagnostics(self):
+        """The last step's max|div u*| before the pressure solve and
+        max|grad phi| (both need log_diagnostics=True) and the mean kinetic
+        energy."""
+        d = self._scal[1:3].cpu().numpy()
+        n = len(self._energy_steps)
+        e = float(self._energy[n - 1].item()) if n else float("nan")
+        return {"pre_div_max": float(d[0]), "grad_max": float(d[1]), "energy_mean": e}
+
+    def _energy_slot(self):
+        k = len(self._energy_steps)
+        if k >= self._energy.numel():
+            grown = torch.zeros(2 * self._energy.numel(), dtype=torch.float64, device=self.device)
+            grown[:k] = self._energy[:k]
+            self._energy = grown
+        return self._energy[k:k + 1]
+
+    def time_step(self):
+        cfg = self.config
+        sp = (cfg.dx, cfg.dy, cfg.dz)
+        diag = cfg.log_diagnostics
+        dt = self.adaptive_time_step()
+        if diag:
+            self._scal[1:3].zero_()
+        # nu_eff = (nu + 0) + art_visc in float32, a scalar (no 3-D LES)
+        nu_eff = np.float32(np.float32(cfg.nu) + np.float32(0.0)) + np.float32(cfg.artificial_viscosity)
+        K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
+                            v_star=self.v_star, w_star=self.w_star, store_tau=False)
+        self.apply_boundary_conditions(self.u_star, self.v_star, self.w_star)
+        K.compute_divergence3d(self.u_star, self.v_star, self.w_star, *sp, out=self.div_u_star,
+                               absmax=self._scal[1:2] if diag else None)
+        self.solve_pressure_fast(self.div_u_star)
+        K.project_velocity3d(self.phi, self.u_star, self.v_star, self.w_star, *sp, dt, u=self.u, v=self.v, w=self.w,
+                             gradmax=self._scal[2:3] if diag else None)
+        self.apply_boundary_conditions(self.u, self.v, self.w)
+        # the energy of the unclipped fields, then the three clips, one launch
+        call("cfd_energy_mean_clip3d_f32", ptr(self.u), ptr(self.v), ptr(self.w), self.u.numel(),
+             ptr(self._energy_slot()), -float(cfg.max_velocity), float(cfg.max_velocity), stream_handle())
+        self._energy_steps.append(self.step)
+        self.times.append(self.step * dt)
+        self.step += 1
+        return dt
+
+
+def monitor_simulation_health3d(solver: LidDrivenCavity3DSolver, step: int) -> bool:
+    """monitor_simulation_health's thresholds (v5.py:599-613) on u, v, w:
+    non-finite values, max|V| > max_velocity, max|div| above 20 (step <= 1000)
+    or 2 (after); device reductions with one host read."""
+    cfg = solver.config
+    s = stream_handle()
+    n = solver.u.numel()
+    cnt = torch.zeros(2, dtype=torch.int32, device=solver.device)
+    red = torch.zeros(2, dtype=torch.float32, device=solver.device)
+    call("cfd_nonfinite_count_f32", ptr(solver.u), ptr(solver.v), n, ptr(cnt[0:1]), s)
+    call("cfd_nonfinite_count_f32", ptr(solver.w), None, n, ptr(cnt[1:2]), s)
+    for f in (solver.u, solver.v, solver.w):
+        call("cfd_absmax_f32", ptr(f), n, ptr(red[0:1]), s)  # the max accumulates
+    div = torch.empty_like(solver.u)
+    call("cfd_divergence3d_f32", ptr(solver.u), ptr(solver.v), ptr(solver.w), ptr(div), cfg.nz, cfg.ny, cfg.nx,
+         float(cfg.dx), float(cfg.dy), float(cfg.dz), ptr(red[1:2]), s)
+    n_bad = int(cnt.sum().item())
+    vel_max, div_max = (float(x) for x in red.cpu().numpy())
+    if n_bad:
+        return False
+    if vel_max > cfg.max_velocity:
+        return False
+    div_threshold = 20.0 if step <= 1000 else 2.0
+    return not (div_max > div_threshold)
 
 
 def monitor_simulation_health(solver: OptimizedTurbulentSolver, step: int) -> bool:

@@ -312,6 +312,85 @@ int cfd_numpy_powf_f32(const float *x, float y, float *out, size_t n, void *stre
 /* count of non-finite values in a and b (v5.py:601), into a device int. */
 int cfd_nonfinite_count_f32(const float *a, const float *b, size_t n, int *out, void *stream);
 
+/* ------------------------------------------------- 3-D projection step */
+/* The incompressible step around the 3-D pressure solves (cfd_jacobi3d_zero_f32,
+ * cfd_rbgs3d_f32) on float32 fields u, v, w of layout (nz, ny, nx), x fastest:
+ * E/W = x+-1, N/S = y+-1, U/D = z+-1.  The reference is 2-D only; this is the
+ * build's own generalisation of the v5 templates above, every 2-D coefficient
+ * kept and a z term appended to each sum (tests/ref3d.py is its NumPy
+ * statement; the kernels give its bits).  Single GPU; all indexing is 64-bit
+ * (1024^3 fields are 4 GiB).  Every dimension must be >= 3 (ny, nz <= 65535),
+ * required pointers non-NULL and no output may alias an input or another
+ * output: CFD_E_INVALID otherwise, before any launch.
+ *
+ * Constants, formed in double and rounded once to float: h = min(dx, dy, dz);
+ * sdx = 0.5/dx, c1x = 0.5*sdx, c2x = sdx*sdx, ux = 1/dx, lx = 1/(dx*dx) and
+ * their y, z analogues; eps = 1e-10f.
+ *
+ * Fused predictor.  On interior cells, with (uc, vc, wc) the centre velocities
+ * and for each field f in {u, v, w} with neighbours E, W, N, S, U, D of C:
+ *   tau (use_supg): vm = sqrt((uc*uc + vc*vc) + wc*wc), correctly rounded;
+ *     vm > eps: pe = (vm*h)/(nu_eff + eps), half = pe/2, lim = min(half, 1),
+ *     tau = (h/(2*vm))*lim (IEEE divisions); else tau = dt/2
+ *   SUPG convection: ddx = (E-W)*c1x, ddy = (N-S)*c1y, ddz = (U-D)*c1z,
+ *     cs = (uc*ddx + vc*ddy) + wc*ddz; tau > 0: conv = cs - tau*((uc*d2x +
+ *     vc*d2y) + wc*d2z) with d2x = ((E - 2*C) + W)*c2x (likewise y, z); else cs
+ *   upwind convection (use_supg = 0): ddx = uc > 0 ? (C-W)*ux : (E-C)*ux, ddy by
+ *     vc with S / N, ddz by wc with D / U; conv = (uc*ddx + vc*ddy) + wc*ddz
+ *   lap = nu_eff*((l1 + l2) + l3), l1 = ((E - 2*C) + W)*lx (likewise y, z)
+ *   f_star = f + dt*(-conv + lap)
+ * On the six faces f_star = f and tau = 0.  nu_eff is a scalar ((nu + 0) +
+ * art_visc; no 3-D LES).  tau may be NULL (not stored); with use_supg = 0 a
+ * given tau is filled with zeros.  Algorithmic traffic: 24 B per cell (28 with
+ * tau). */
+int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff,
+                        float *u_star, float *v_star, float *w_star, float *tau,
+                        int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                        int use_supg, void *stream);
+/* Kernel of cfd_predictor3d_f32 (tuning, per host thread; the same bits either
+ * way; cfd_reset_tuning restores auto): variant 0 = auto (the plane march --
+ * a wave owns 64 x cells_per_lane columns and a few rows and marches along z
+ * with three planes of u, v, w in registers -- where nx % cells_per_lane == 0
+ * and the arrays' alignment leave it 2 or 4 cells per lane; else one thread
+ * per cell), 1 = one thread per cell, 2 = the plane march at whatever width
+ * fits (a plane must stay below 2^31 bytes); rows = rows per wave of the march
+ * (0 = auto: 2; 1, 2); cells_per_lane = adjacent cells per lane (0 = auto: 4,
+ * 2 below 256 columns; 1, 2, 4), halved until nx % it == 0 and every array is
+ * aligned to it elements. */
+int cfd_set_predictor3d_config(int variant, int rows, int cells_per_lane);
+/* The calling thread's last cfd_predictor3d_f32 launch: returns 1 = plane
+ * march, 0 = one thread per cell, -1 = none yet; *cells_per_lane of that
+ * launch (may be NULL). */
+int cfd_get_last_predictor3d_path(int *cells_per_lane);
+/* div = ((uE - uW)*cx + (vN - vS)*cy) + (wU - wD)*cz on the interior with
+ * cx = f32(0.5/dx) (likewise cy, cz), 0 on the six faces.  absmax (device
+ * float*, optional): receives max|div|; must be zeroed by the caller. */
+int cfd_divergence3d_f32(const float *u, const float *v, const float *w, float *div,
+                         int nz, int ny, int nx, double dx, double dy, double dz,
+                         float *absmax, void *stream);
+/* Gradient + projection: gx = (phiE - phiW)*cx, gy = (phiN - phiS)*cy,
+ * gz = (phiU - phiD)*cz, then u = u_star - dt*gx, v = v_star - dt*gy,
+ * w = w_star - dt*gz on the interior; the six faces copy u_star, v_star,
+ * w_star through.  gradmax (optional, zeroed by the caller):
+ * max sqrt((gx*gx + gy*gy) + gz*gz). */
+int cfd_project3d_f32(const float *phi, const float *u_star, const float *v_star,
+                      const float *w_star, float *u, float *v, float *w,
+                      int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                      float *gradmax, void *stream);
+/* Lid-driven cavity walls in 3-D (the pattern of cfd_apply_lid_bc2d_f32):
+ * u = v = w = 0 on all six faces, then u = u_lid, v = w = 0 on the face
+ * y = ny - 1, written last: the lid owns its edges. */
+int cfd_apply_lid_bc3d_f32(float *u, float *v, float *w, int nz, int ny, int nx, float u_lid,
+                           void *stream);
+/* The float64 mean of 0.5*((u*u + v*v) + w*w) over n cells (each cell's energy
+ * formed in float32 from the unclipped values, float64 partial sums in a fixed
+ * order: the same bits run to run; out need not be zeroed) followed by the
+ * three np.clip(., lo, hi) calls, in one launch, as cfd_energy_mean_clip2d_f32
+ * does for two fields.  Its partial sums live in static device memory, one
+ * slot per (device, stream) in use: up to 32 streams per device. */
+int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *out,
+                               float lo, float hi, void *stream);
+
 /* --------------------------------------------------- float64 fields */
 /* memory_efficient=False (v5.py:287-296): every field float64; the kernels
  * below are the *_f32 ones above with float64 arrays, the same argument
@@ -620,7 +699,8 @@ int cfd_get_last_tbr_shape(int *levels, int *row_waves, int *rows_per_wave, int 
 int cfd_timing_enable(int enable);
 int cfd_timing_read(double *ms, long long *sweeps, int reset);
 /* The same for one channel: 0 = the pressure solves (cfd_timing_read), 1 =
- * the predictor launches (cfd_predictor2d_f32 / _f64 / _les_*, one count per launch),
+ * the predictor launches (cfd_predictor2d_f32 / _f64 / _les_*,
+ * cfd_predictor3d_f32; one count per launch),
  * so a timed time_step reports the solve's sweeps without the predictor in
  * them.  reset clears the channel read (the other channel's timings stay). */
 int cfd_timing_read_channel(int channel, double *ms, long long *sweeps, int reset);
