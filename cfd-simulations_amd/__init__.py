@@ -20,6 +20,7 @@ __version__ = "0.1.0"
 
 from .solver import (OptimizedTurbulentConfig, OptimizedTurbulentSolver,  # noqa: F401
                      monitor_simulation_health, host_grid, host_masks, host_potential_flow,
-                     LidDrivenCavity3DConfig, LidDrivenCavity3DSolver, monitor_simulation_health3d)
+                     LidDrivenCavity3DConfig, LesCavity3DConfig, LidDrivenCavity3DSolver,
+                     monitor_simulation_health3d)
 from .slab import SlabPlan  # noqa: F401
 from . import kernels  # noqa: F401

@@ -33,21 +33,37 @@ __device__ inline bool interior3(int k, int j, int i, int nz, int ny, int nx) {
 
 // The fused predictor, one thread per cell (plain loads; the neighbours come
 // from L1 / L2): the fallback of the plane march for unaligned shapes and its
-// yardstick.  pred3_tau / pred3_cell: pred_planes.hpp.
-template <bool SUPG>
+// yardstick.  pred3_tau / pred3_cell / smag3_nut: pred_planes.hpp.  NM: the
+// viscosity mode (kNu3Scalar: nu; kNu3Array: nu_arr per cell; kNu3Les:
+// (nu + nu_t) + art with nu_t formed here and written to nut unless null).
+struct Pred3Nu {
+    const float *nu_arr;
+    float *nut;
+    float c2, art;
+};
+// M: one Pred3Nu for the array and LES modes, empty for the scalar one (whose
+// argument list, and with it its code, stays what it was before the modes)
+template <bool SUPG, int NM, typename... M>
 __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u, const float *__restrict__ v,
                                                      const float *__restrict__ w, float nu,
                                                      float *__restrict__ us, float *__restrict__ vs,
                                                      float *__restrict__ ws, float *__restrict__ tau_out, int nz,
-                                                     int ny, int nx, float dt, PredK3 kk) {
+                                                     int ny, int nx, float dt, PredK3 kk, M... mode) {
     CFD_3D_INDEX
     if (!cell) return;
     const float uc = u[c], vc = v[c], wc = w[c];
-    float uo = uc, vo = vc, wo = wc, t = 0.0f;  // the six faces keep f (tau: 0)
+    float uo = uc, vo = vc, wo = wc, t = 0.0f;  // the six faces keep f (tau, nu_t: 0)
+    [[maybe_unused]] float nt = 0.0f;
+    [[maybe_unused]] const Pred3Nu m = {mode...};
     if (interior3(k, j, i, nz, ny, nx)) {
         const Nb7 fu = {uc, u[c + 1], u[c - 1], u[c + sy], u[c - sy], u[c + sz], u[c - sz]};
         const Nb7 fv = {vc, v[c + 1], v[c - 1], v[c + sy], v[c - sy], v[c + sz], v[c - sz]};
         const Nb7 fw = {wc, w[c + 1], w[c - 1], w[c + sy], w[c - sy], w[c + sz], w[c - sz]};
+        if constexpr (NM == kNu3Array) nu = m.nu_arr[c];
+        if constexpr (NM == kNu3Les) {
+            nt = smag3_nut(fu, fv, fw, m.c2, kk);
+            nu = (nu + nt) + m.art;
+        }
         if (SUPG) t = pred3_tau(uc, vc, wc, nu, dt, kk);
         uo = pred3_cell<SUPG>(uc, vc, wc, fu, t, nu, dt, kk);
         vo = pred3_cell<SUPG>(uc, vc, wc, fv, t, nu, dt, kk);
@@ -57,6 +73,25 @@ __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u
     vs[c] = vo;
     ws[c] = wo;
     if (tau_out) tau_out[c] = t;  // zeros without SUPG
+    if constexpr (NM == kNu3Les)
+        if (m.nut) m.nut[c] = nt;
+}
+
+// smag3_nut on the interior, 0 on the six faces
+__global__ __launch_bounds__(256) void k_smagorinsky3d(const float *__restrict__ u, const float *__restrict__ v,
+                                                       const float *__restrict__ w, float *__restrict__ nut, int nz,
+                                                       int ny, int nx, float c2, PredK3 kk) {
+    CFD_3D_INDEX
+    if (!cell) return;
+    float nt = 0.0f;
+    if (interior3(k, j, i, nz, ny, nx)) {
+        // only C, E, N, U are read
+        const Nb7 fu = {u[c], u[c + 1], 0.0f, u[c + sy], 0.0f, u[c + sz], 0.0f};
+        const Nb7 fv = {v[c], v[c + 1], 0.0f, v[c + sy], 0.0f, v[c + sz], 0.0f};
+        const Nb7 fw = {w[c], w[c + 1], 0.0f, w[c + sy], 0.0f, w[c + sz], 0.0f};
+        nt = smag3_nut(fu, fv, fw, c2, kk);
+    }
+    nut[c] = nt;
 }
 
 // ((uE - uW) cx + (vN - vS) cy) + (wU - wD) cz, 0 on the six faces (+ max|div|)
@@ -237,20 +272,23 @@ using namespace cfd;
 
 extern "C" {
 
-int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
-                        float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
-                        double dz, float dt, int use_supg, void *stream) {
-    CFD_REQUIRE(u && v && w && u_star && v_star && w_star, "predictor3d: null pointer");
-    CFD_SHAPE3D("predictor3d", nz, ny, nx);
-    const float *in[3] = {u, v, w};
-    float *out[4] = {u_star, v_star, w_star, tau};
-    for (int o = 0; o < 4; ++o) {
-        for (int q = 0; q < 3; ++q)
-            CFD_REQUIRE(out[o] != in[q], "predictor3d: outputs must not alias inputs");
-        for (int p = 0; p < o; ++p)
-            CFD_REQUIRE(!out[o] || out[o] != out[p], "predictor3d: outputs must not alias each other");
+// The three entry points of the fused predictor (nm: the viscosity mode).
+// nu_arr (kNu3Array) is an input, nut (kNu3Les, may be null) an output.
+static int predictor3d_run(const char *who, int nm, const float *u, const float *v, const float *w, float nu,
+                           const float *nu_arr, float art, double cs, float *u_star, float *v_star, float *w_star,
+                           float *tau, float *nut, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                           int use_supg, void *stream) {
+    CFD_REQUIRE(u && v && w && u_star && v_star && w_star && (nm != kNu3Array || nu_arr), "%s: null pointer", who);
+    CFD_SHAPE3D(who, nz, ny, nx);
+    const float *in[4] = {u, v, w, nu_arr};
+    float *out[5] = {u_star, v_star, w_star, tau, nut};
+    for (int o = 0; o < 5; ++o) {
+        if (!out[o]) continue;
+        for (int q = 0; q < 4; ++q) CFD_REQUIRE(out[o] != in[q], "%s: outputs must not alias inputs", who);
+        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "%s: outputs must not alias each other", who);
     }
     const PredK3 k = make_pred_k3(dx, dy, dz);
+    const float c2 = nm == kNu3Les ? (float)smag3_const(cs, dx, dy, dz) : 0.0f;
     hipStream_t s = as_stream(stream);
     // cells per lane of the plane march: the preferred count (tuning; auto: 4,
     // 2 where a 256-column segment would be wider than the grid), halved until
@@ -260,7 +298,8 @@ int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu
     auto fits = [&](int c) {
         const uintptr_t m = (uintptr_t)(4 * c - 1);
         auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
-        return nx % c == 0 && al(u) && al(v) && al(w) && al(u_star) && al(v_star) && al(w_star) && al(tau);
+        return nx % c == 0 && al(u) && al(v) && al(w) && al(u_star) && al(v_star) && al(w_star) && al(tau) &&
+               al(nu_arr) && al(nut);
     };
     while (vec > 1 && !fits(vec)) vec /= 2;
     // the march runs where a plane's byte offsets fit its buffer resource and
@@ -269,6 +308,10 @@ int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu
     const bool plane_ok = (size_t)ny * nx * sizeof(float) < ((size_t)1 << 31);
     const int variant = tuning().pred3_variant;
     const bool march = plane_ok && variant != 1 && (variant == 2 || vec > 1);
+    // LES with SUPG is the one instantiation where arithmetic shows: where the
+    // march runs, auto takes it at one cell per lane (the fastest measured
+    // shape at 512^3 SUPG); a given cells_per_lane is kept
+    if (march && nm == kNu3Les && use_supg && !tuning().pred3_vec) vec = 1;
     const int tk = timing_begin(s, kTimingPredictor);
     if (march) {
         Pred3Args a;
@@ -279,27 +322,73 @@ int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu
         a.vs = v_star;
         a.ws = w_star;
         a.tau = tau;
-        a.nu = nu_eff;
+        a.nu = nu;
         a.dt = dt;
         a.nz = nz;
         a.ny = ny;
         a.nx = nx;
         a.k = k;
+        a.nu_arr = nu_arr;
+        a.nut = nut;
+        a.c2 = c2;
+        a.art = art;
         const int rows = tuning().pred3_rows ? tuning().pred3_rows : 2;
-        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, vec, rows, 0, s));
+        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, nm, vec, rows, 0, s));
         g_last_pred3[0] = 1;
         g_last_pred3[1] = vec;
     } else {
-        if (use_supg)
-            hipLaunchKernelGGL(k_predictor3d<true>, grid3d(nz, ny, nx), dim3(256), 0, s, u, v, w, nu_eff, u_star,
-                               v_star, w_star, tau, nz, ny, nx, dt, k);
-        else
-            hipLaunchKernelGGL(k_predictor3d<false>, grid3d(nz, ny, nx), dim3(256), 0, s, u, v, w, nu_eff, u_star,
-                               v_star, w_star, tau, nz, ny, nx, dt, k);
+        const Pred3Nu m = {nu_arr, nut, c2, art};
+        const dim3 g = grid3d(nz, ny, nx);
+#define CFD_PRED3_CELL(KERNEL, ...)                                                                        \
+    hipLaunchKernelGGL(KERNEL, g, dim3(256), 0, s, u, v, w, nu, u_star, v_star, w_star, tau, nz, ny, nx, dt, k, \
+                       ##__VA_ARGS__)
+        if (nm == kNu3Les) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, Pred3Nu>), m);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, Pred3Nu>), m);
+        } else if (nm == kNu3Array) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Array, Pred3Nu>), m);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Array, Pred3Nu>), m);
+        } else {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar>));
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar>));
+        }
+#undef CFD_PRED3_CELL
         g_last_pred3[0] = 0;
         g_last_pred3[1] = 1;
     }
     timing_end(tk, s, 1);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
+                        float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
+                        double dz, float dt, int use_supg, void *stream) {
+    return predictor3d_run("predictor3d", kNu3Scalar, u, v, w, nu_eff, nullptr, 0.0f, 0.0, u_star, v_star, w_star, tau,
+                           nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+}
+
+int cfd_predictor3d_nu_f32(const float *u, const float *v, const float *w, const float *nu_eff, float *u_star,
+                           float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
+                           double dz, float dt, int use_supg, void *stream) {
+    return predictor3d_run("predictor3d_nu", kNu3Array, u, v, w, 0.0f, nu_eff, 0.0f, 0.0, u_star, v_star, w_star, tau,
+                           nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+}
+
+int cfd_predictor3d_les_f32(const float *u, const float *v, const float *w, float nu, float art_visc, double cs,
+                            float *u_star, float *v_star, float *w_star, float *tau, float *nu_t, int nz, int ny,
+                            int nx, double dx, double dy, double dz, float dt, int use_supg, void *stream) {
+    return predictor3d_run("predictor3d_les", kNu3Les, u, v, w, nu, nullptr, art_visc, cs, u_star, v_star, w_star, tau,
+                           nu_t, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+}
+
+int cfd_smagorinsky3d_f32(const float *u, const float *v, const float *w, float *nu_t, int nz, int ny, int nx,
+                          double dx, double dy, double dz, double cs, void *stream) {
+    CFD_REQUIRE(u && v && w && nu_t, "smagorinsky3d: null pointer");
+    CFD_REQUIRE(nu_t != u && nu_t != v && nu_t != w, "smagorinsky3d: nu_t must not alias an input");
+    CFD_SHAPE3D("smagorinsky3d", nz, ny, nx);
+    hipLaunchKernelGGL(k_smagorinsky3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, nu_t, nz, ny, nx,
+                       (float)smag3_const(cs, dx, dy, dz), make_pred_k3(dx, dy, dz));
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

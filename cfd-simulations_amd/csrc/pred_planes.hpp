@@ -22,6 +22,16 @@
 // save 8 of 24 row loads per plane and field, all of them cache hits, for two
 // barriers per plane.  u*, v*, w* and tau leave as streaming stores.
 //
+// Viscosity modes (NM).  kNu3Array: the cell's nu_eff is read from an array of
+// the fields' shape -- the R own rows of its plane, loaded one plane ahead, no
+// halo.  kNu3Les: the Smagorinsky nu_t of the cell (smag3_nut) is formed from
+// values the march holds anyway -- E: the lane's next cell or the DPP shift
+// with the halo cell as `old`, N: row[r + 2], U: the plane k + 1 -- so LES
+// costs no extra read; nu_t is zeroed on the side columns by the `in`
+// predicate (face rows and planes are wave-uniform) and leaves as a streaming
+// store through its own per-plane buffer resource.  The scalar instantiations
+// are unchanged by the other two modes (if constexpr throughout).
+//
 // Indexing is 64-bit: each plane gets its own buffer resource (base pointer
 // advanced by k * ny * nx elements in 64 bits, one plane's bytes as the
 // range), so offsets stay below 2^31 on arrays of any size; a plane outside
@@ -78,6 +88,35 @@ struct Nb7 {
     float C, E, W, N, S, U, D;
 };
 
+// Viscosity of the predictor: one scalar for every cell (kNu3Scalar), an
+// array of the fields' shape read per cell (kNu3Array), or LES (kNu3Les):
+// the Smagorinsky nu_t of the cell formed from values the kernel holds anyway,
+// then nu_eff = (nu + nu_t) + art_visc per cell.
+enum { kNu3Scalar = 0, kNu3Array = 1, kNu3Les = 2 };
+
+// The project's own 3-D form of compute_smagorinsky_viscosity_fast (the
+// reference is 2-D and ships with LES off; tests/les3d_reference.py states
+// this arithmetic): forward differences of u, v, w to the east, north and up
+// neighbours, q = 2 (ux^2 + vy^2 + wz^2) + (uy + vx)^2 + (uz + wx)^2 +
+// (vz + wy)^2 in the order below, nu_t = c2 sqrt(q) with the sqrt correctly
+// rounded; c2 = float(smag3_const).  One interior cell.
+__device__ inline float smag3_nut(const Nb7 &u, const Nb7 &v, const Nb7 &w, float c2, const PredK3 &k) {
+    const float dux = (u.E - u.C) * k.ux, duy = (u.N - u.C) * k.uy, duz = (u.U - u.C) * k.uz;
+    const float dvx = (v.E - v.C) * k.ux, dvy = (v.N - v.C) * k.uy, dvz = (v.U - v.C) * k.uz;
+    const float dwx = (w.E - w.C) * k.ux, dwy = (w.N - w.C) * k.uy, dwz = (w.U - w.C) * k.uz;
+    const float d = (dux * dux + dvy * dvy) + dwz * dwz;
+    const float sxy = duy + dvx, sxz = duz + dwx, syz = dvz + dwy;
+    const float o = (sxy * sxy + sxz * sxz) + syz * syz;
+    const float q = 2.0f * d + o;
+    return c2 * sqrt_ieee(q);
+}
+// (cs * (dx*dy*dz) ** (1.0/3.0)) ** 2 in Python floats: both `**` are libm's
+// pow (exponents kept opaque, as in smag_const); the caller rounds it to float
+inline double smag3_const(double cs, double dx, double dy, double dz) {
+    volatile double third = 1.0 / 3.0, two = 2.0;
+    return std::pow(cs * std::pow(dx * dy * dz, third), two);
+}
+
 // f* = f + dt * (-conv + lap) of one interior cell of field f (uc, vc, wc: the
 // centre velocities; t: the cell's tau, SUPG only)
 template <bool SUPG>
@@ -114,6 +153,11 @@ struct Pred3Args {
     int nz, ny, nx;
     int zchunk, nseg, ntile;  // planes per chunk, segments per row, row tiles (4 waves x R rows)
     PredK3 k;
+    // kNu3Array: nu_eff per cell.  kNu3Les: nu_eff = (nu + nu_t) + art with
+    // nu_t = c2 sqrt(q) (smag3_nut); nut: null = not written
+    const float *nu_arr;
+    float *nut;
+    float c2, art;
 };
 
 // rows j0 - 1 .. j0 + R of one plane of one field (index 0 = row j0 - 1) and
@@ -124,7 +168,7 @@ struct Plane {
     float halo[R];
 };
 
-template <int VEC, int R, bool SUPG>
+template <int VEC, int R, bool SUPG, int NM = kNu3Scalar>
 __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
     constexpr int SW = 64 * VEC;  // segment width (columns)
     const int lane = threadIdx.x & (kWave - 1);
@@ -190,7 +234,20 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
     }
     Plane<VEC, R> Uc = load_plane(a.u, z0), Vc = load_plane(a.v, z0), Wc = load_plane(a.w, z0);
     Plane<VEC, R> Up = load_plane(a.u, z0 + 1), Vp = load_plane(a.v, z0 + 1), Wp = load_plane(a.w, z0 + 1);
+    // kNu3Array: the R own rows of nu_eff, one plane ahead (no halo)
+    [[maybe_unused]] Cells<float, VEC> Nc[R];
+    if constexpr (NM == kNu3Array) {
+        const __amdgpu_buffer_rsrc_t rn = prsrc(a.nu_arr, z0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) Nc[r] = pldv<float, VEC>(rn, ro[r + 1]);
+    }
     for (int z = z0; z < z1; ++z) {
+        [[maybe_unused]] Cells<float, VEC> Nn[R];
+        if constexpr (NM == kNu3Array) {
+            const __amdgpu_buffer_rsrc_t rn = prsrc(a.nu_arr, z + 1 < z1 ? z + 1 : -1);
+#pragma unroll
+            for (int r = 0; r < R; ++r) Nn[r] = pldv<float, VEC>(rn, ro[r + 1]);
+        }
         // two planes ahead
         const Plane<VEC, R> Un = load_plane(a.u, z + 2), Vn = load_plane(a.v, z + 2), Wn = load_plane(a.w, z + 2);
         const bool zin = z >= 1 && z <= nz - 2;  // wave-uniform
@@ -200,11 +257,15 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
         const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(a.ws + pofs, 0, pbytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rt =
             __builtin_amdgcn_make_buffer_rsrc(a.tau ? a.tau + pofs : a.us, 0, a.tau ? pbytes : 0, 0x00020000);
+        [[maybe_unused]] __amdgpu_buffer_rsrc_t rnt = rt;
+        if constexpr (NM == kNu3Les)
+            rnt = __builtin_amdgcn_make_buffer_rsrc(a.nut ? a.nut + pofs : a.us, 0, a.nut ? pbytes : 0, 0x00020000);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int j = j0 + r;
-            // the six faces keep f (tau: 0)
+            // the six faces keep f (tau, nu_t: 0)
             Cells<float, VEC> uo = Uc.row[r + 1], vo = Vc.row[r + 1], wo = Wc.row[r + 1], to = {};
+            [[maybe_unused]] Cells<float, VEC> no = {};
             if (zin && j >= 1 && j <= ny - 2) {  // wave-uniform
                 const float *uc = Uc.row[r + 1].x, *vc = Vc.row[r + 1].x, *wc = Wc.row[r + 1].x;
 #pragma unroll
@@ -231,12 +292,19 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
                     fv.D = Vm[r].x[c];
                     fw.U = Wp.row[r + 1].x[c];
                     fw.D = Wm[r].x[c];
-                    float t = 0.0f;
-                    if constexpr (SUPG) t = pred3_tau(uc[c], vc[c], wc[c], nu, dt, a.k);
-                    const float nu_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fu, t, nu, dt, a.k);
-                    const float nv_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fv, t, nu, dt, a.k);
-                    const float nw_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fw, t, nu, dt, a.k);
                     const bool in = x0 + c >= 1 && x0 + c <= nx - 2;
+                    float ne = nu;  // the cell's nu_eff
+                    if constexpr (NM == kNu3Array) ne = Nc[r].x[c];
+                    if constexpr (NM == kNu3Les) {
+                        const float nt = smag3_nut(fu, fv, fw, a.c2, a.k);
+                        ne = (nu + nt) + a.art;
+                        no.x[c] = in ? nt : 0.0f;
+                    }
+                    float t = 0.0f;
+                    if constexpr (SUPG) t = pred3_tau(uc[c], vc[c], wc[c], ne, dt, a.k);
+                    const float nu_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fu, t, ne, dt, a.k);
+                    const float nv_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fv, t, ne, dt, a.k);
+                    const float nw_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fw, t, ne, dt, a.k);
                     uo.x[c] = in ? nu_ : uc[c];
                     vo.x[c] = in ? nv_ : vc[c];
                     wo.x[c] = in ? nw_ : wc[c];
@@ -248,6 +316,8 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
             pstv<float, VEC>(vo, rvs, o);
             pstv<float, VEC>(wo, rws, o);
             if (a.tau) pstv<float, VEC>(to, rt, o);  // zeros without SUPG
+            if constexpr (NM == kNu3Les)
+                if (a.nut) pstv<float, VEC>(no, rnt, o);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -261,24 +331,37 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
         Up = Un;
         Vp = Vn;
         Wp = Wn;
+        if constexpr (NM == kNu3Array) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) Nc[r] = Nn[r];
+        }
     }
 }
 
+template <int VEC, int R, int NM>
+inline const void *pred_planes_kernel_nm(bool supg) {
+    return supg ? (const void *)k_predictor3d_planes<VEC, R, true, NM>
+                : (const void *)k_predictor3d_planes<VEC, R, false, NM>;
+}
 template <int VEC, int R>
-inline const void *pred_planes_kernel(bool supg) {
-    return supg ? (const void *)k_predictor3d_planes<VEC, R, true> : (const void *)k_predictor3d_planes<VEC, R, false>;
+inline const void *pred_planes_kernel(bool supg, int nm) {
+    if (nm == kNu3Array) return pred_planes_kernel_nm<VEC, R, kNu3Array>(supg);
+    if (nm == kNu3Les) return pred_planes_kernel_nm<VEC, R, kNu3Les>(supg);
+    return pred_planes_kernel_nm<VEC, R, kNu3Scalar>(supg);
 }
 
 // Plane-march launch: cells per lane vec (1, 2, 4), rows per wave rows (1, 2),
 // planes per chunk zchunk (0: auto); a.nseg / a.ntile / a.zchunk are filled
 // here.  The caller has checked shape (a plane below 2^31 bytes, nx % vec == 0)
 // and alignment.
-inline hipError_t pred_planes_launch(Pred3Args a, bool supg, int vec, int rows, int zchunk, hipStream_t s) {
+inline hipError_t pred_planes_launch(Pred3Args a, bool supg, int nm, int vec, int rows, int zchunk, hipStream_t s) {
     const void *f;
     if (rows == 1)
-        f = vec == 4 ? pred_planes_kernel<4, 1>(supg) : (vec == 2 ? pred_planes_kernel<2, 1>(supg) : pred_planes_kernel<1, 1>(supg));
+        f = vec == 4 ? pred_planes_kernel<4, 1>(supg, nm)
+                     : (vec == 2 ? pred_planes_kernel<2, 1>(supg, nm) : pred_planes_kernel<1, 1>(supg, nm));
     else
-        f = vec == 4 ? pred_planes_kernel<4, 2>(supg) : (vec == 2 ? pred_planes_kernel<2, 2>(supg) : pred_planes_kernel<1, 2>(supg));
+        f = vec == 4 ? pred_planes_kernel<4, 2>(supg, nm)
+                     : (vec == 2 ? pred_planes_kernel<2, 2>(supg, nm) : pred_planes_kernel<1, 2>(supg, nm));
     a.nseg = ceil_div(a.nx, 64 * vec);
     a.ntile = ceil_div(a.ny, 4 * rows);
     // planes per chunk: each chunk re-reads 2 planes, so long chunks, but at

@@ -25,6 +25,7 @@ __all__ = [
     "solve_pressure_jacobi3d_zero",
     "solve_pressure_gauss_seidel3d", "persistent_failures",
     "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
+    "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
 ]
 
 
@@ -412,7 +413,8 @@ def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=Non
                       tau=None, store_tau=True):
     """The 3-D fused predictor (cfd_predictor3d_f32): SUPG tau, convection and
     Laplacian of u, v, w and f_star = f + dt*(-conv + lap) in one pass, the six
-    faces copied through.  ``nu_eff`` is a scalar.  Returns (u_star, v_star,
+    faces copied through.  ``nu_eff`` is a scalar, or a tensor of the fields'
+    shape read per cell (cfd_predictor3d_nu_f32).  Returns (u_star, v_star,
     w_star, tau); arrays not given are allocated.  ``store_tau=False`` with no
     ``tau`` given: tau is not stored (24 B per cell instead of 28) and None is
     returned for it.  Without SUPG a stored tau is zeros."""
@@ -421,11 +423,53 @@ def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=Non
     ws = torch.empty_like(u) if w_star is None else w_star
     if tau is None and store_tau:
         tau = torch.empty_like(u)
+    if isinstance(nu_eff, torch.Tensor) and nu_eff.dim() > 0:
+        nz, ny, nx = _fields3d(u, v=v, w=w, nu_eff=nu_eff, u_star=us, v_star=vs, w_star=ws, tau=tau)
+        call("cfd_predictor3d_nu_f32", ptr(u), ptr(v), ptr(w), ptr(nu_eff), ptr(us), ptr(vs), ptr(ws), ptr(tau),
+             nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle())
+        return us, vs, ws, tau
     nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau)
     call("cfd_predictor3d_f32", ptr(u), ptr(v), ptr(w), float(np.float32(nu_eff)), ptr(us), ptr(vs), ptr(ws),
          ptr(tau), nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)),
          stream_handle())
     return us, vs, ws, tau
+
+
+def compute_smagorinsky_viscosity3d(u, v, w, dx, dy, dz, cs, out=None):
+    """The Smagorinsky eddy viscosity in 3-D (cfd_smagorinsky3d_f32): nu_t =
+    (cs (dx dy dz)**(1/3))**2 |S| from forward differences to the east, north
+    and up neighbours, 0 on the six faces -- the project's own 3-D form of
+    compute_smagorinsky_viscosity_fast (the reference is 2-D; the arithmetic
+    is stated in tests/les3d_reference.py).  ``out``: an optional array of
+    u's shape to write into (not an input).  Returns nu_t."""
+    nu_t = torch.empty_like(u) if out is None else out
+    nz, ny, nx = _fields3d(u, v=v, w=w, out=nu_t)
+    call("cfd_smagorinsky3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), nz, ny, nx, float(dx), float(dy), float(dz),
+         float(cs), stream_handle())
+    return nu_t
+
+
+def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=True, u_star=None, v_star=None,
+                          w_star=None, tau=None, nu_t=None, store_tau=True, store_nu_t=True):
+    """The 3-D LES predictor (cfd_predictor3d_les_f32) in one pass: nu_t =
+    compute_smagorinsky_viscosity3d(u, v, w, ...), nu_eff = (nu + nu_t) +
+    art_visc per cell in float32, then predictor3d_fused with that array --
+    the same bits as those calls, with nu_t formed from the values the kernel
+    holds anyway.  Returns (u_star, v_star, w_star, tau, nu_t); arrays not
+    given are allocated, unless ``store_tau`` / ``store_nu_t`` is False: that
+    array is then not stored and None is returned for it."""
+    us = torch.empty_like(u) if u_star is None else u_star
+    vs = torch.empty_like(u) if v_star is None else v_star
+    ws = torch.empty_like(u) if w_star is None else w_star
+    if tau is None and store_tau:
+        tau = torch.empty_like(u)
+    if nu_t is None and store_nu_t:
+        nu_t = torch.empty_like(u)
+    nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau, nu_t=nu_t)
+    call("cfd_predictor3d_les_f32", ptr(u), ptr(v), ptr(w), float(np.float32(nu)), float(np.float32(art_visc)),
+         float(cs), ptr(us), ptr(vs), ptr(ws), ptr(tau), ptr(nu_t), nz, ny, nx, float(dx), float(dy), float(dz),
+         _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle())
+    return us, vs, ws, tau, nu_t
 
 
 def compute_divergence3d(u, v, w, dx, dy, dz, out=None, absmax=None):

@@ -18,6 +18,8 @@ arithmetic (tests/les_reference.py); parity with the reference is unpinned.
 
 ``LidDrivenCavity3DSolver`` is the same projection step in 3-D around the 3-D
 pressure solves (the project's own generalisation: the reference is 2-D only).
+With a ``LesCavity3DConfig`` it runs the 3-D LES predictor
+(``K.predictor3d_fused_les``; pinned to tests/les3d_reference.py).
 
 Out of scope: plotting and video (OptimizedVisualizer),
 and HDF5 output (h5py is absent; ``save_snapshot`` writes the same layout to
@@ -520,14 +522,27 @@ class LidDrivenCavity3DConfig(OptimizedTurbulentConfig):
     lid_velocity: float = 1.0
     output_dir: str = "cavity3d_re_100"
     hdf5_file: str = "cavity3d_re_100.h5"
+    _accepts_les = False  # LesCavity3DConfig: True
 
     def __post_init__(self):
         super().__post_init__()
         self.dz = (self.z_max - self.z_min) / (self.nz - 1)
-        if self.use_les:
-            raise ValueError("LidDrivenCavity3DConfig: LES is 2-D only")
+        if self.use_les and not self._accepts_les:
+            raise ValueError("LidDrivenCavity3DConfig: LES is 2-D only (3-D LES: LesCavity3DConfig)")
         if not self.memory_efficient:
             raise ValueError("LidDrivenCavity3DConfig: the 3-D step is float32 only (memory_efficient=True)")
+
+
+@dataclass
+class LesCavity3DConfig(LidDrivenCavity3DConfig):
+    """LidDrivenCavity3DConfig with LES: the Smagorinsky eddy viscosity in its
+    3-D form (K.compute_smagorinsky_viscosity3d; the project's own statement,
+    tests/les3d_reference.py -- the reference is 2-D and ships with LES off)
+    formed inside the predictor, nu_eff = (nu + nu_t) + artificial_viscosity
+    per cell.  use_les=False behaves exactly like the base config."""
+    use_les: bool = True
+    smagorinsky_constant: float = 0.17
+    _accepts_les = True
 
 
 class LidDrivenCavity3DSolver:
@@ -542,7 +557,13 @@ class LidDrivenCavity3DSolver:
     kinetic energy and the three clips.  No host synchronisation, except the
     adaptive dt's one read of max|V| from step 1000 on.
 
-    Out of scope: snapshots, LES, immersed boundaries or masks, float64, a
+    LES (a LesCavity3DConfig with use_les=True): the predictor is
+    K.predictor3d_fused_les, which forms the Smagorinsky nu_t of the step's
+    u, v, w per cell and keeps it in ``nu_t``; from step 1000 on the adaptive
+    dt reads the float64 mean of the previous step's nu_t together with
+    max|V| in the same single host read.
+
+    Out of scope: snapshots, immersed boundaries or masks, float64, a
     slab-decomposed (multi-GPU) step, and the 2-D step's clean_divergence
     stage (a v5 quirk with serial semantics that does not generalise)."""
 
@@ -566,24 +587,43 @@ class LidDrivenCavity3DSolver:
         self._energy_steps = []
         self.times = []
         self.step = 0
+        self.use_les = bool(cfg.use_les)
+        if self.use_les:
+            self.nu_t = z()
+            # LES adaptive dt: [mean nu_t (float64), max|V| (float32, first bytes)]: one host read
+            self._dt_red = torch.zeros(2, dtype=torch.float64, device=self.device)
 
     def adaptive_time_step(self):
-        """The v5 rule (v5.py:316-326) with max(|u|, |v|, |w|) and min(dx, dy, dz)."""
+        """The v5 rule (v5.py:316-326) with max(|u|, |v|, |w|) and min(dx, dy, dz);
+        with LES, np.mean(nu_t) of the previous step's nu_t as a float64 device
+        mean rounded to float32, fetched with max|V| in the one host read."""
         cfg = self.config
         if not cfg.adaptive_dt:
             return cfg.dt_base
         if self.step < 1000:
             return np.float32(0.00002)
         s = stream_handle()
-        out = self._scal[0:1]
-        out.zero_()
         n = self.u.numel()
+        if self.use_les:
+            self._dt_red.zero_()
+            out = self._dt_red[1:2].view(self.dtype)[0:1]
+        else:
+            out = self._scal[0:1]
+            out.zero_()
         call("cfd_absmax2_f32", ptr(self.u), ptr(self.v), n, ptr(out), s)
         call("cfd_absmax_f32", ptr(self.w), n, ptr(out), s)  # the max accumulates
-        vel_max = max(np.float32(out.item()), 1e-10)  # the one host read of the step
+        if self.use_les:
+            K.mean64(self.nu_t, out=self._dt_red[0:1])
+            red = self._dt_red.cpu().numpy()  # the one host read of the step
+            vmax = red[1:2].view(np.float32)[0]
+            nu_t_mean = np.float32(red[0])
+        else:
+            vmax = np.float32(out.item())  # the one host read of the step
+            nu_t_mean = np.float32(0.0)
+        vel_max = max(vmax, 1e-10)
         h = min(cfg.dx, cfg.dy, cfg.dz)
         dt_cfl = cfg.cfl_target * h / vel_max
-        nu_total = cfg.nu + np.float32(0.0) + cfg.artificial_viscosity
+        nu_total = cfg.nu + nu_t_mean + cfg.artificial_viscosity
         dt_visc = 0.4 * h ** 2 / nu_total
         return np.float32(np.clip(min(dt_cfl, dt_visc), cfg.dt_min, cfg.dt_max))
 
@@ -640,10 +680,17 @@ class LidDrivenCavity3DSolver:
         dt = self.adaptive_time_step()
         if diag:
             self._scal[1:3].zero_()
-        # nu_eff = (nu + 0) + art_visc in float32, a scalar (no 3-D LES)
-        nu_eff = np.float32(np.float32(cfg.nu) + np.float32(0.0)) + np.float32(cfg.artificial_viscosity)
-        K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
-                            v_star=self.v_star, w_star=self.w_star, store_tau=False)
+        if self.use_les:
+            # nu_t of u, v, w formed inside the predictor and kept in self.nu_t;
+            # nu_eff = (nu + nu_t) + art_visc per cell in float32
+            K.predictor3d_fused_les(self.u, self.v, self.w, *sp, dt, cfg.nu, cfg.artificial_viscosity,
+                                    cfg.smagorinsky_constant, cfg.use_supg, u_star=self.u_star,
+                                    v_star=self.v_star, w_star=self.w_star, nu_t=self.nu_t, store_tau=False)
+        else:
+            # nu_eff = (nu + 0) + art_visc in float32, a scalar
+            nu_eff = np.float32(np.float32(cfg.nu) + np.float32(0.0)) + np.float32(cfg.artificial_viscosity)
+            K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
+                                v_star=self.v_star, w_star=self.w_star, store_tau=False)
         self.apply_boundary_conditions(self.u_star, self.v_star, self.w_star)
         K.compute_divergence3d(self.u_star, self.v_star, self.w_star, *sp, out=self.div_u_star,
                                absmax=self._scal[1:2] if diag else None)

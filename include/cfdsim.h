@@ -340,15 +340,56 @@ int cfd_nonfinite_count_f32(const float *a, const float *b, size_t n, int *out, 
  *   lap = nu_eff*((l1 + l2) + l3), l1 = ((E - 2*C) + W)*lx (likewise y, z)
  *   f_star = f + dt*(-conv + lap)
  * On the six faces f_star = f and tau = 0.  nu_eff is a scalar ((nu + 0) +
- * art_visc; no 3-D LES).  tau may be NULL (not stored); with use_supg = 0 a
- * given tau is filled with zeros.  Algorithmic traffic: 24 B per cell (28 with
- * tau). */
+ * art_visc: LES off); cfd_predictor3d_nu_f32 takes it per cell and
+ * cfd_predictor3d_les_f32 forms it from the Smagorinsky nu_t.  tau may be NULL
+ * (not stored); with use_supg = 0 a given tau is filled with zeros.
+ * Algorithmic traffic: 24 B per cell (28 with tau). */
 int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff,
                         float *u_star, float *v_star, float *w_star, float *tau,
                         int nz, int ny, int nx, double dx, double dy, double dz, float dt,
                         int use_supg, void *stream);
-/* Kernel of cfd_predictor3d_f32 (tuning, per host thread; the same bits either
- * way; cfd_reset_tuning restores auto): variant 0 = auto (the plane march --
+/* The same with nu_eff an array of the fields' shape, read once per cell (the
+ * cell's own value enters its tau and its Laplacian factor; no halo): for a
+ * caller that supplies a viscosity field, and the second half of the
+ * composition cfd_predictor3d_les_f32 is defined by.  nu_eff must not be an
+ * output.  28 B per cell (32 with tau). */
+int cfd_predictor3d_nu_f32(const float *u, const float *v, const float *w, const float *nu_eff,
+                           float *u_star, float *v_star, float *w_star, float *tau,
+                           int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                           int use_supg, void *stream);
+/* The Smagorinsky eddy viscosity in 3-D: the build's own 3-D form of
+ * compute_smagorinsky_viscosity_fast (v5.py:96-110).  The reference is 2-D and
+ * ships with LES off, so this is pinned to the project's own statement
+ * (tests/les3d_reference.py), not to the reference.  Float32 operations in
+ * this order, with kx = f32(1/dx), ky, kz (the predictor's ux, uy, uz) and
+ * forward differences fx = (f[E] - f[C])*kx, fy = (f[N] - f[C])*ky,
+ * fz = (f[U] - f[C])*kz of f = u, v, w:
+ *   d = (ux*ux + vy*vy) + wz*wz
+ *   sxy = uy + vx, sxz = uz + wx, syz = vz + wy
+ *   o = (sxy*sxy + sxz*sxz) + syz*syz
+ *   q = 2*d + o;  nu_t = c2 * sqrt(q), the sqrt correctly rounded (subnormal q
+ *   included), c2 = f32((cs * (dx*dy*dz) ** (1.0/3.0)) ** 2) formed in Python
+ *   floats (`**` = libm pow) and rounded once
+ * on the interior; nu_t = 0 on the six faces.  On z-invariant u, v with w = 0
+ * q is the 2-D q of cfd_smagorinsky2d_f32 bit for bit.  nu_t must not alias an
+ * input.  64-bit indexing. */
+int cfd_smagorinsky3d_f32(const float *u, const float *v, const float *w, float *nu_t,
+                          int nz, int ny, int nx, double dx, double dy, double dz, double cs,
+                          void *stream);
+/* The fused predictor with LES: cfd_smagorinsky3d_f32's nu_t of u, v, w, then
+ * nu_eff = (nu + nu_t) + art_visc per cell in float32, then
+ * cfd_predictor3d_nu_f32's arithmetic -- the same bits as those three steps.
+ * Both kernels form nu_t per cell from the neighbours they hold anyway (no
+ * extra read) and store it with tau; nu_t and tau may each be NULL (not
+ * stored).  cs = 0 gives cfd_predictor3d_f32's bits with the scalar (nu + 0) +
+ * art_visc.  28 B per cell with nu_t stored and tau not. */
+int cfd_predictor3d_les_f32(const float *u, const float *v, const float *w, float nu,
+                            float art_visc, double cs, float *u_star, float *v_star,
+                            float *w_star, float *tau, float *nu_t, int nz, int ny, int nx,
+                            double dx, double dy, double dz, float dt, int use_supg, void *stream);
+/* Kernel of cfd_predictor3d_f32 / _nu_f32 / _les_f32 (tuning, per host
+ * thread; the same bits either way; cfd_reset_tuning restores auto):
+ * variant 0 = auto (the plane march --
  * a wave owns 64 x cells_per_lane columns and a few rows and marches along z
  * with three planes of u, v, w in registers -- where nx % cells_per_lane == 0
  * and the arrays' alignment leave it 2 or 4 cells per lane; else one thread
@@ -356,11 +397,13 @@ int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu
  * fits (a plane must stay below 2^31 bytes); rows = rows per wave of the march
  * (0 = auto: 2; 1, 2); cells_per_lane = adjacent cells per lane (0 = auto: 4,
  * 2 below 256 columns; 1, 2, 4), halved until nx % it == 0 and every array is
- * aligned to it elements. */
+ * aligned to it elements.  One exception, measured: cfd_predictor3d_les_f32
+ * with use_supg and cells_per_lane = 0 runs the march at 1 cell per lane
+ * wherever the rule above runs the march at all. */
 int cfd_set_predictor3d_config(int variant, int rows, int cells_per_lane);
-/* The calling thread's last cfd_predictor3d_f32 launch: returns 1 = plane
- * march, 0 = one thread per cell, -1 = none yet; *cells_per_lane of that
- * launch (may be NULL). */
+/* The calling thread's last cfd_predictor3d_f32 / _nu_f32 / _les_f32 launch:
+ * returns 1 = plane march, 0 = one thread per cell, -1 = none yet;
+ * *cells_per_lane of that launch (may be NULL). */
 int cfd_get_last_predictor3d_path(int *cells_per_lane);
 /* div = ((uE - uW)*cx + (vN - vS)*cy) + (wU - wD)*cz on the interior with
  * cx = f32(0.5/dx) (likewise cy, cz), 0 on the six faces.  absmax (device
@@ -700,7 +743,7 @@ int cfd_timing_enable(int enable);
 int cfd_timing_read(double *ms, long long *sweeps, int reset);
 /* The same for one channel: 0 = the pressure solves (cfd_timing_read), 1 =
  * the predictor launches (cfd_predictor2d_f32 / _f64 / _les_*,
- * cfd_predictor3d_f32; one count per launch),
+ * cfd_predictor3d_f32 / _nu_f32 / _les_f32; one count per launch),
  * so a timed time_step reports the solve's sweeps without the predictor in
  * them.  reset clears the channel read (the other channel's timings stay). */
 int cfd_timing_read_channel(int channel, double *ms, long long *sweeps, int reset);

@@ -1,0 +1,445 @@
+"""3-D LES on the GPU against its NumPy statement (tests/les3d_reference.py):
+the stand-alone Smagorinsky kernel, the array-nu mode of the fused predictor,
+the fused LES predictor (one thread per cell and every shape of the plane
+march), and whole steps of LidDrivenCavity3DSolver on a LesCavity3DConfig
+against Cavity3DLesReference.  Bar: BIT-EXACT fields, nu_t and dt; the mean
+kinetic energy to 1e-6 relative (the float64 device mean's bar, as in
+tests/test_gpu_step3d.py).  The reference project is 2-D and ships with LES
+off: this path is pinned to the project's own statement.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from cfd_simulations_amd import _lib
+from cfd_simulations_amd import kernels as K
+from cfd_simulations_amd._lib import call, ptr, stream_handle
+from cfd_simulations_amd.solver import LesCavity3DConfig, LidDrivenCavity3DConfig, LidDrivenCavity3DSolver
+from les3d_reference import (Cavity3DLesReference, nu_eff3d_numpy, predictor3d_les_numpy, predictor3d_nu_numpy,
+                             smag3d_q_numpy, smagorinsky3d_numpy)
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+SP = dict(dx=0.013, dy=0.011, dz=0.017)
+SPT = (SP["dx"], SP["dy"], SP["dz"])
+NU, ART, CS, DT = F(0.011), F(0.001), 0.17, F(2e-3)
+SHAPES = [(3, 3, 3), (5, 6, 7), (9, 11, 132), (20, 37, 264)]
+MARCH_SHAPES = SHAPES[2:]
+MARCH_CONFIGS = [(rows, cpl) for cpl in (1, 2, 4) for rows in (1, 2)]
+OUT = ("u_star", "v_star", "w_star", "tau", "nu_t")
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a, order="C")).to("cuda")  # a writable copy
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def fields(shape):
+    """N(0, 1) velocities with a block of exact zeros (q = 0) and a block of
+    values near 1e-21 whose differences make q subnormal."""
+    rng = np.random.default_rng(100 + sum(shape))
+    u, v, w = (rng.standard_normal(shape).astype(F) for _ in range(3))
+    nz, ny, nx = shape
+    if min(shape) >= 5:
+        z, j, i = slice(1, 3), slice(1, 3), slice(1, min(nx - 1, 70))
+        u[z, j, i], v[z, j, i], w[z, j, i] = 0, 0, 0
+        z, j, i = slice(nz - 3, nz), slice(ny - 3, ny), slice(max(1, nx - 70), nx)
+        n = u[z, j, i].shape
+        u[z, j, i] = (F(1e-21) * (1 + rng.random(n))).astype(F)
+        v[z, j, i] = (F(-1e-21) * (1 + rng.random(n))).astype(F)
+        w[z, j, i] = (F(1e-21) * (1 + rng.random(n))).astype(F)
+    for f in (u, v, w):
+        f.setflags(write=False)
+    return u, v, w
+
+
+@functools.lru_cache(maxsize=None)
+def nut_ref(shape):
+    r = smagorinsky3d_numpy(*fields(shape), cs=CS, **SP)
+    r.setflags(write=False)
+    return r
+
+
+@functools.lru_cache(maxsize=None)
+def les_ref(shape, supg):
+    out = predictor3d_les_numpy(*fields(shape), NU, ART, CS, dt=DT, use_supg=supg, **SP)
+    assert np.array_equal(out["nu_t"], nut_ref(shape))
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def nu_field(shape):
+    """A positive viscosity field for the array mode, unrelated to u, v, w."""
+    rng = np.random.default_rng(7 + sum(shape))
+    a = (F(0.002) + F(0.02) * rng.random(shape)).astype(F)
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def nu_ref(shape, supg):
+    out = predictor3d_nu_numpy(*fields(shape), nu_field(shape), dt=DT, use_supg=supg, **SP)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def last_path():
+    cpl = ctypes.c_int(0)
+    return _lib.lib().cfd_get_last_predictor3d_path(ctypes.byref(cpl)), cpl.value
+
+
+def eq(got, want, what, equal_nan=False):
+    assert np.array_equal(host(got), want, equal_nan=equal_nan), what
+
+
+def check_nu(shape, supg, label=""):
+    ref = nu_ref(shape, supg)
+    u, v, w = (dev(f) for f in fields(shape))
+    ne = dev(nu_field(shape))
+    for store_tau in (True, False):
+        got = K.predictor3d_fused(u, v, w, *SPT, DT, ne, supg, store_tau=store_tau)
+        for name, t in zip(OUT[:3], got):
+            eq(t, ref[name], (name, shape, supg, store_tau, label))
+        if store_tau:
+            eq(got[3], ref["tau"], ("tau", shape, supg, label))
+        else:
+            assert got[3] is None
+    return last_path()
+
+
+def check_les(shape, supg, label=""):
+    ref = les_ref(shape, supg)
+    u, v, w = (dev(f) for f in fields(shape))
+    for store_tau, store_nu_t in ((True, True), (False, True), (True, False), (False, False)):
+        got = K.predictor3d_fused_les(u, v, w, *SPT, DT, NU, ART, CS, supg, store_tau=store_tau,
+                                      store_nu_t=store_nu_t)
+        for name, t, stored in zip(OUT, got, (True, True, True, store_tau, store_nu_t)):
+            if stored:
+                eq(t, ref[name], (name, shape, supg, store_tau, store_nu_t, label))
+            else:
+                assert t is None
+    return last_path()
+
+
+@pytest.fixture(autouse=True)
+def default_tuning():
+    call("cfd_reset_tuning")
+    yield
+    call("cfd_reset_tuning")
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_smagorinsky3d_bitexact(shape):
+    u, v, w = (dev(f) for f in fields(shape))
+    ref = nut_ref(shape)
+    got = host(K.compute_smagorinsky_viscosity3d(u, v, w, *SPT, CS))
+    assert np.array_equal(got, ref)
+    face = np.ones(shape, bool)
+    face[1:-1, 1:-1, 1:-1] = False
+    assert not got[face].any() and (got[~face] > 0).any()
+    if min(shape) >= 5:   # the q = 0 block, and subnormal q with a non-zero root
+        assert (got[1, 1, 1:3] == 0).all()
+        sub = (slice(-3, -1), slice(-3, -1), slice(-4, -1))
+        q = np.zeros(shape, F)
+        q[1:-1, 1:-1, 1:-1] = smag3d_q_numpy(*fields(shape), **SP)
+        q = q[sub]
+        assert (q > 0).all() and (q < np.finfo(F).tiny).any()
+        assert (got[sub] > 0).all() and (got[sub] < 1e-20).all()
+    out = torch.full(shape, -1.0, dtype=torch.float32, device="cuda")
+    assert K.compute_smagorinsky_viscosity3d(u, v, w, *SPT, CS, out=out) is out
+    assert np.array_equal(host(out), ref)
+
+
+@pytest.mark.parametrize("supg", [True, False])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_array_nu_and_les_default_path_bitexact(shape, supg):
+    want = ((1,), (2, 4)) if shape in MARCH_SHAPES else ((0,), (1,))
+    path, cpl = check_nu(shape, supg)
+    assert path in want[0] and cpl in want[1]
+    path, cpl = check_les(shape, supg)
+    if shape in MARCH_SHAPES and supg:   # LES with SUPG: auto marches at one cell per lane
+        assert (path, cpl) == (1, 1)
+    else:
+        assert path in want[0] and cpl in want[1]
+    call("cfd_set_predictor3d_config", 0, 0, 4)   # a given width is kept
+    assert check_les(shape, supg) == ((1, 4) if shape in MARCH_SHAPES else (0, 1))
+
+
+@pytest.mark.parametrize("supg", [True, False])
+@pytest.mark.parametrize("shape", MARCH_SHAPES)
+def test_array_nu_every_variant_same_bits(shape, supg):
+    call("cfd_set_predictor3d_config", 1, 0, 0)
+    assert check_nu(shape, supg, "per cell") == (0, 1)
+    for rows, cpl in MARCH_CONFIGS:
+        call("cfd_set_predictor3d_config", 2, rows, cpl)
+        assert check_nu(shape, supg, (rows, cpl)) == (1, cpl)
+
+
+@pytest.mark.parametrize("supg", [True, False])
+@pytest.mark.parametrize("shape", MARCH_SHAPES)
+def test_les_every_variant_same_bits(shape, supg):
+    call("cfd_set_predictor3d_config", 1, 0, 0)
+    assert check_les(shape, supg, "per cell") == (0, 1)
+    for rows, cpl in MARCH_CONFIGS:
+        call("cfd_set_predictor3d_config", 2, rows, cpl)
+        assert check_les(shape, supg, (rows, cpl)) == (1, cpl)
+    call("cfd_reset_tuning")
+    assert check_les(shape, supg, "reset")[0] == 1
+
+
+@pytest.mark.parametrize("supg", [True, False])
+@pytest.mark.parametrize("shape", SHAPES[1:])
+def test_les_equals_the_composition(shape, supg):
+    """Stand-alone nu_t kernel, elementwise nu_eff in torch float32, array
+    mode: the fused call's bits, on the per-cell kernel and the march."""
+    u, v, w = (dev(f) for f in fields(shape))
+    nt = K.compute_smagorinsky_viscosity3d(u, v, w, *SPT, CS)
+    ne = (nt + float(NU)) + float(ART)
+    assert ne.dtype == torch.float32
+    for variant in (0, 1):
+        call("cfd_set_predictor3d_config", variant, 0, 0)
+        comp = K.predictor3d_fused(u, v, w, *SPT, DT, ne, supg)
+        fused = K.predictor3d_fused_les(u, v, w, *SPT, DT, NU, ART, CS, supg)
+        for name, a, b in zip(OUT[:4], comp, fused):
+            assert np.array_equal(host(a), host(b)), (name, shape, supg, variant)
+        assert np.array_equal(host(fused[4]), host(nt))
+
+
+def test_cs_zero_gives_the_scalar_predictor_bits():
+    shape = (9, 11, 132)
+    u, v, w = (dev(f) for f in fields(shape))
+    want = K.predictor3d_fused(u, v, w, *SPT, DT, F(NU + F(0.0)) + ART, True)
+    got = K.predictor3d_fused_les(u, v, w, *SPT, DT, NU, ART, 0.0, True)
+    for a, b in zip(want, got):
+        assert np.array_equal(host(a), host(b))
+    assert not host(got[4]).any()
+
+
+def test_misaligned_views_fall_back():
+    """Views one element into a buffer are 4-byte aligned only: the march
+    halves its width down to 1 and auto takes the per-cell kernel."""
+    shape = (9, 11, 132)
+    n = int(np.prod(shape))
+    view = lambda: torch.empty(n + 1, dtype=torch.float32, device="cuda")[1:].view(shape)  # noqa: E731
+    ins = [view().copy_(dev(f)) for f in fields(shape)]
+    ne = view().copy_(dev(nu_field(shape)))
+    outs = [view() for _ in range(5)]
+    for variant, want in ((0, (0, 1)), (2, (1, 1))):
+        call("cfd_set_predictor3d_config", variant, 0, 0)
+        K.predictor3d_fused_les(*ins, *SPT, DT, NU, ART, CS, True, u_star=outs[0], v_star=outs[1], w_star=outs[2],
+                                tau=outs[3], nu_t=outs[4])
+        assert last_path() == want
+        for name, t in zip(OUT, outs):
+            eq(t, les_ref(shape, True)[name], (name, variant))
+        K.predictor3d_fused(*ins, *SPT, DT, ne, True, u_star=outs[0], v_star=outs[1], w_star=outs[2], tau=outs[3])
+        assert last_path() == want
+        for name, t in zip(OUT[:4], outs):
+            eq(t, nu_ref(shape, True)[name], (name, variant, "array"))
+    # only nu_t misaligned: the same fall-back
+    call("cfd_reset_tuning")
+    al = [dev(f) for f in fields(shape)]
+    K.predictor3d_fused_les(*al, *SPT, DT, NU, ART, CS, True, nu_t=outs[4], store_tau=False)
+    assert last_path() == (0, 1)
+    eq(outs[4], nut_ref(shape), "nu_t")
+    K.predictor3d_fused(*al, *SPT, DT, ne, True, store_tau=False)
+    assert last_path() == (0, 1)
+
+
+@pytest.mark.parametrize("supg", [True, False])
+def test_nonfinite_and_huge_inputs(supg):
+    shape = (9, 11, 132)
+    u, v, w = (np.array(f) for f in fields(shape))
+    u[2, 3, 5], v[4, 5, 64], w[6, 7, 100] = F(1e20), F(-1e20), F(1e20)
+    u[3, 4, 70], v[5, 6, 128], w[2, 2, 2] = np.inf, -np.inf, np.nan
+    u[7, 9, 130] = np.nan
+    ref = predictor3d_les_numpy(u, v, w, NU, ART, CS, dt=DT, use_supg=supg, **SP)
+    assert np.isnan(ref["nu_t"]).any() and np.isinf(ref["nu_t"]).any()
+    du, dv, dw = dev(u), dev(v), dev(w)
+    for cfg in ((1, 0, 0), (2, 2, 4), (2, 1, 2), (2, 2, 1)):
+        call("cfd_set_predictor3d_config", *cfg)
+        got = K.predictor3d_fused_les(du, dv, dw, *SPT, DT, NU, ART, CS, supg)
+        for name, t in zip(OUT, got):
+            eq(t, ref[name], (name, cfg), equal_nan=True)
+    eq(K.compute_smagorinsky_viscosity3d(du, dv, dw, *SPT, CS), ref["nu_t"], "nu_t", equal_nan=True)
+    ne = nu_eff3d_numpy(ref["nu_t"], NU, ART)
+    refn = predictor3d_nu_numpy(u, v, w, ne, dt=DT, use_supg=supg, **SP)
+    for cfg in ((1, 0, 0), (2, 2, 4)):
+        call("cfd_set_predictor3d_config", *cfg)
+        got = K.predictor3d_fused(du, dv, dw, *SPT, DT, dev(ne), supg)
+        for name, t in zip(OUT[:4], got):
+            eq(t, refn[name], (name, cfg, "array"), equal_nan=True)
+
+
+def test_les_counts_on_the_predictor_timing_channel():
+    shape = (9, 11, 132)
+    u, v, w = (dev(f) for f in fields(shape))
+    ne = dev(nu_field(shape))
+    ms, n = ctypes.c_double(0), ctypes.c_longlong(0)
+    call("cfd_timing_enable", 1)
+    try:
+        call("cfd_timing_read_channel", 1, ctypes.byref(ms), ctypes.byref(n), 1)
+        K.predictor3d_fused_les(u, v, w, *SPT, DT, NU, ART, CS)
+        K.predictor3d_fused(u, v, w, *SPT, DT, ne)
+        call("cfd_set_predictor3d_config", 1, 0, 0)
+        K.predictor3d_fused_les(u, v, w, *SPT, DT, NU, ART, CS)
+        call("cfd_timing_read_channel", 1, ctypes.byref(ms), ctypes.byref(n), 1)
+    finally:
+        call("cfd_timing_enable", 0)
+    assert n.value == 3 and ms.value > 0
+
+
+def test_invalid_arguments_are_refused_on_the_host():
+    L = _lib.lib()
+    s = stream_handle()
+    t = [torch.zeros((4, 5, 6), dtype=torch.float32, device="cuda") for _ in range(9)]
+    p = [ptr(x) for x in t]
+    sp = (0.1, 0.1, 0.1)
+
+    def variants(fn, ok):
+        assert fn(*ok) == 0
+
+        def f(**kw):
+            a = list(ok)
+            for i, val in kw.items():
+                a[int(i[1:])] = val
+            return fn(*a)
+        return f
+
+    les = variants(L.cfd_predictor3d_les_f32,
+                   (p[0], p[1], p[2], 0.01, 0.001, 0.17, p[3], p[4], p[5], p[6], p[7], 4, 5, 6, *sp, 1e-3, 1, s))
+    assert les(a9=None, a10=None) == 0                                  # tau, nu_t: optional
+    assert les(a6=p[0]) == -1 and b"alias" in L.cfd_last_error()        # u_star is u
+    assert les(a10=p[1]) == -1 and les(a10=p[6]) == -1 and les(a10=p[3]) == -1   # nu_t is v / tau / u_star
+    assert les(a9=p[2]) == -1 and les(a7=p[3]) == -1
+    assert les(a1=None) == -1 and b"null" in L.cfd_last_error()
+    assert les(a8=None) == -1
+    for i in (11, 12, 13):
+        assert les(**{f"a{i}": 2}) == -1
+    arr = variants(L.cfd_predictor3d_nu_f32,
+                   (p[0], p[1], p[2], p[8], p[3], p[4], p[5], p[6], 4, 5, 6, *sp, 1e-3, 1, s))
+    assert arr(a7=None) == 0
+    assert arr(a3=None) == -1 and b"null" in L.cfd_last_error()
+    assert arr(a4=p[8]) == -1 and b"alias" in L.cfd_last_error()        # u_star is nu_eff
+    assert arr(a7=p[8]) == -1 and arr(a5=p[0]) == -1 and arr(a6=p[4]) == -1
+    for i in (8, 9, 10):
+        assert arr(**{f"a{i}": 2}) == -1
+    smag = variants(L.cfd_smagorinsky3d_f32, (p[0], p[1], p[2], p[3], 4, 5, 6, *sp, 0.17, s))
+    assert smag(a3=None) == -1 and smag(a0=None) == -1
+    for i in (0, 1, 2):
+        assert smag(a3=p[i]) == -1 and b"alias" in L.cfd_last_error()
+    for i in (4, 5, 6):
+        assert smag(**{f"a{i}": 2}) == -1
+    # the checked wrappers: a mis-shaped or mistyped companion never reaches the library
+    small = torch.zeros((4, 5, 5), dtype=torch.float32, device="cuda")
+    f64 = torch.zeros((4, 5, 6), dtype=torch.float64, device="cuda")
+    for bad in (small, f64):
+        with pytest.raises(ValueError):
+            K.predictor3d_fused(t[0], t[1], t[2], *sp, 1e-3, bad)
+        with pytest.raises(ValueError):
+            K.predictor3d_fused_les(t[0], t[1], t[2], *sp, 1e-3, 0.01, 0.001, 0.17, nu_t=bad)
+        with pytest.raises(ValueError):
+            K.compute_smagorinsky_viscosity3d(t[0], t[1], t[2], *sp, 0.17, out=bad)
+    with pytest.raises(ValueError):
+        K.predictor3d_fused(t[0], t[1], t[2], *sp, 1e-3, t[3].transpose(1, 2).contiguous().transpose(1, 2))
+    torch.cuda.synchronize()
+
+
+CUBE = dict(nz=17, ny=25, nx=33, z_max=0.5, y_max=0.75, x_max=1.0, pressure_iterations=40)
+STEP_CASES = {
+    "jacobi-supg": dict(CUBE),
+    "jacobi-upwind": dict(CUBE, use_supg=False),
+    "rbgs-noncubic": dict(CUBE, y_max=1.0, use_fast_pressure=True, pressure_iterations=60, pressure_tolerance=1e-8),
+}
+FIELDS = ("u", "v", "w", "phi", "u_star", "v_star", "w_star", "div_u_star")
+
+
+def compare_step(g, o, k, names=FIELDS + ("nu_t",)):
+    dg, do = g.time_step(), o.time_step()
+    assert dg == do and type(dg) is type(do), k
+    for f in names:
+        a, b = getattr(g, f), getattr(o, f)
+        assert np.array_equal(host(a), b if isinstance(b, np.ndarray) else host(b)), (f, k)
+
+
+@pytest.mark.parametrize("case", list(STEP_CASES))
+def test_les_cavity3d_steps_bitexact(case):
+    c = LesCavity3DConfig(log_diagnostics=True, **STEP_CASES[case])
+    assert c.use_les and c.smagorinsky_constant == 0.17
+    g, o = LidDrivenCavity3DSolver(c), Cavity3DLesReference(c)
+    for k in range(4):
+        compare_step(g, o, k)
+        assert bool(host(g.nu_t).any()) == (k >= 1), k   # the fluid starts at rest
+        d = g.diagnostics
+        for key in ("pre_div_max", "grad_max"):
+            assert F(d[key]) == o.diagnostics[key], (key, k)
+    g.step = o.step = 1000   # the adaptive-dt branch: the mean of step 3's nu_t enters
+    assert np.mean(o.nu_t, dtype=np.float64) > 0
+    compare_step(g, o, 1000)
+    assert g.step == o.step == 1001 and host(g.nu_t).any()
+    e = np.array([v for _, v in g.energy_history])
+    e_ref = np.array([v for _, v in o.energy_history])
+    assert (e_ref[1:] > 0).all() and np.allclose(e, e_ref, rtol=1e-6, atol=0)
+
+
+def test_les_adaptive_dt_takes_the_nu_t_mean():
+    """A large nu_t mean makes the viscous limit the active one: dt follows it."""
+    c = LesCavity3DConfig(**CUBE)
+    g, o = LidDrivenCavity3DSolver(c), Cavity3DLesReference(c)
+    rng = np.random.default_rng(4)
+    nt = (rng.random((c.nz, c.ny, c.nx)) * 20).astype(F)
+    g.nu_t.copy_(dev(nt))
+    o.nu_t = nt
+    g.step = o.step = 1000
+    dg, do = g.adaptive_time_step(), o.adaptive_time_step()
+    assert dg == do and c.dt_min < dg < c.dt_max
+
+
+@pytest.mark.parametrize("les_off", ["cs=0", "use_les=False"])
+def test_les_off_equals_the_base_solver(les_off):
+    kw = dict(smagorinsky_constant=0.0) if les_off == "cs=0" else dict(use_les=False)
+    g = LidDrivenCavity3DSolver(LesCavity3DConfig(**CUBE, **kw))
+    b = LidDrivenCavity3DSolver(LidDrivenCavity3DConfig(**CUBE))
+    assert g.use_les == (les_off == "cs=0")
+    for k in (0, 1, 2, 1000):
+        if k == 1000:
+            g.step = b.step = 1000
+        compare_step(g, b, k, FIELDS)
+    assert g.energy_history == b.energy_history and g.energy_history[-1][1] > 0
+
+
+def test_les_cavity3d_step_replays_from_a_graph():
+    """One LES time_step (step < 1000: no host read) captured into a graph and
+    replayed gives the eager step's bits."""
+    c = LesCavity3DConfig(log_diagnostics=True, **CUBE)
+    g, e = LidDrivenCavity3DSolver(c), LidDrivenCavity3DSolver(c)
+    for _ in range(2):
+        g.time_step()
+        e.time_step()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        LidDrivenCavity3DSolver(c).time_step()   # the side stream's first call, outside the capture
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        g.time_step()
+    graph.replay()
+    e.time_step()
+    torch.cuda.synchronize()
+    assert g.step == e.step == 3
+    for f in FIELDS + ("nu_t",):
+        assert np.array_equal(host(getattr(g, f)), host(getattr(e, f))), f
+    assert host(g.nu_t).any()
+    assert g.diagnostics == e.diagnostics and g.energy_history[-1] == e.energy_history[-1]
