@@ -99,6 +99,10 @@ PROTOTYPES = {
                                   c_float, P, P]),
     "cfd_apply_lid_bc3d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
     "cfd_energy_mean_clip3d_f32": (c_int, [P, P, P, c_size_t, P, c_float, c_float, P]),
+    "cfd_apply_channel_bc_ibm3d_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_int,
+                                               c_double, c_int, c_int, c_int, c_int, P, P]),
+    "cfd_vorticity3d_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
+                                    P]),
     "cfd_supg_tau2d_f64": (c_int, [P, P, P, c_double, P, c_int, c_int, c_double, c_double, c_double, P]),
     "cfd_convection_supg2d_f64": (c_int, [P, P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_convection_upwind2d_f64": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),

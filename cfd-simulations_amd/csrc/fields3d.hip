@@ -1,8 +1,9 @@
 // fields3d.hip -- the 3-D projection step around the 3-D pressure solves, for
 // gfx950: fused advection-diffusion predictor, divergence, gradient +
-// projection, lid-driven cavity walls and the energy / clip epilogue on
-// (nz, ny, nx) float32 fields u, v, w (x fastest; E/W = x+-1, N/S = y+-1,
-// U/D = z+-1).
+// projection, lid-driven cavity walls, the cylinder channel's boundary
+// conditions with the immersed-boundary forcing, the vorticity and the
+// energy / clip epilogue on (nz, ny, nx) float32 fields u, v, w (x fastest;
+// E/W = x+-1, N/S = y+-1, U/D = z+-1).
 //
 // The arithmetic is the project's own 3-D generalisation of the v5 templates
 // (fields2d.hip), every 2-D coefficient kept and a z term appended to each
@@ -171,6 +172,162 @@ __global__ void k_lid_bc3d(float *__restrict__ u, float *__restrict__ v, float *
         put(k * sz + j * sy, lid);
         put(k * sz + j * sy + (nx - 1), lid);
     }
+}
+
+// Channel boundary conditions and the immersed-boundary forcing of the 3-D
+// cylinder channel (axis along z), one launch on u, v, w.  Net effect, in this
+// order (tests/cyl3d_reference.py states it as NumPy): inlet column x = 0
+// (u = k_bc's inlet value of row i, v = w = 0), outlet copy nx-1 <- nx-2,
+// free-slip spanwise faces (u, v of planes 0 / nz-1 <- planes 1 / nz-2, w = 0),
+// channel walls i = 0 and ny-1 at 0 (written last), then ibm_cell with the 2-D
+// float64 mask m[i, j] on every plane.
+//
+// Ownership: every cell is written by one thread and no thread reads a cell
+// another one writes.  The owners are the cells (k, i, j) with 1 <= k <= nz-2
+// and j <= nx-2: an owner forms its value after the walls ("before"), applies
+// the IBM factor, and also writes the cells that copy from it -- (k, i, nx-1)
+// when j == nx-2, and the same cells of plane 0 when k == 1 and of plane nz-1
+// when k == nz-2 (nz == 3: both).  A cell (k', i, j') belongs to the owner
+// (clamp(k', 1, nz-2), i, min(j', nx-2)).  Only owners with something to write
+// are visited, in four disjoint index ranges: planes 1 and nz-2 whole; on the
+// planes between them the wall rows, the columns 0 and nx-2, and the box
+// [i0, i1) x [j0, j1) of the mask clipped to the cells left over.  The mask is
+// read inside the box only (0 elsewhere), so the stage costs its faces plus
+// the box and not a pass over the fields.
+struct BcIbm3 {
+    float *u, *v, *w;
+    const double *y, *m;
+    int nz, ny, nx;
+    double y_max, v_inf;
+    int step;
+    double fs;
+    int i0, i1, j0, j1;
+    double *force;  // += sum (before - after) of u, v, w over the cells with m > 0
+};
+
+__device__ inline void bc_ibm3_own(const BcIbm3 &a, int k, int i, int j, double (&f)[3]) {
+    const size_t sy = (size_t)a.nx, sz = (size_t)a.ny * a.nx;
+    const size_t c = (size_t)k * sz + (size_t)i * sy + j;
+    auto mk = [&](int jj) {
+        return a.m && i >= a.i0 && i < a.i1 && jj >= a.j0 && jj < a.j1 ? a.m[(size_t)i * sy + jj] : 0.0;
+    };
+    const bool wall = i == 0 || i == a.ny - 1, east = j == a.nx - 2;
+    const bool keep = !wall && j != 0;  // the assignments leave the owner's own value
+    const double mv = mk(j), me = east ? mk(a.nx - 1) : 0.0;
+    if (keep && !east && k != 1 && k != a.nz - 2 && !(mv > 0.0)) return;  // nothing to write
+    float b[3] = {0.0f, 0.0f, 0.0f};
+    if (keep) {
+        b[0] = a.u[c];
+        b[1] = a.v[c];
+        b[2] = a.w[c];
+    } else if (!wall) {  // the inlet, as k_bc forms it
+        const double s = (double)a.step;
+        double scale = s / 1000.0;
+        scale = (1.0 < scale ? 1.0 : scale) * 0.01;
+        const double two_pi = 2.0 * 3.141592653589793;
+        const double pert = scale * sin(two_pi * a.y[i] / a.y_max + 0.02 * s);
+        b[0] = (float)(a.v_inf * (1.0 + pert));
+    }
+    float *const fld[3] = {a.u, a.v, a.w};
+    // one cell: its value before the IBM factor is b (w: 0 on a spanwise face)
+    auto put = [&](size_t cc, double mm, bool face, bool same) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const float before = q == 2 && face ? 0.0f : b[q];
+            const float after = ibm_cell(before, mm, a.fs);
+            if (!same || mm > 0.0) fld[q][cc] = after;
+            if (mm > 0.0) f[q] += (double)before - (double)after;
+        }
+    };
+    put(c, mv, false, keep);
+    if (east) put(c + 1, me, false, false);
+    if (k == 1) {
+        put(c - sz, mv, true, false);
+        if (east) put(c - sz + 1, me, true, false);
+    }
+    if (k == a.nz - 2) {
+        put(c + sz, mv, true, false);
+        if (east) put(c + sz + 1, me, true, false);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_channel_bc_ibm3d(BcIbm3 a, size_t n_plane, size_t n_rows, size_t n_cols,
+                                                          size_t n_box, int bi0, int bj0, int bh, int bw) {
+    __shared__ double part[4][3];
+    double f[3] = {0.0, 0.0, 0.0};
+    const size_t total = n_plane + n_rows + n_cols + n_box;
+    const size_t ex = (size_t)(a.nx - 1);  // owners of a row
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        size_t r = t;
+        if (r < n_plane) {  // planes 1 and nz - 2
+            const int i = (int)(r / ex), j = (int)(r % ex);
+            bc_ibm3_own(a, 1, i, j, f);
+            if (a.nz > 3) bc_ibm3_own(a, a.nz - 2, i, j, f);
+            continue;
+        }
+        r -= n_plane;
+        if (r < n_rows) {  // the wall rows of planes 2 .. nz - 3
+            const int k = 2 + (int)(r / (2 * ex));
+            const size_t q = r % (2 * ex);
+            bc_ibm3_own(a, k, q < ex ? 0 : a.ny - 1, (int)(q % ex), f);
+            continue;
+        }
+        r -= n_rows;
+        if (r < n_cols) {  // columns 0 and nx - 2 of rows 1 .. ny - 2 of those planes
+            const size_t per = 2 * (size_t)(a.ny - 2);
+            const int k = 2 + (int)(r / per);
+            const size_t q = r % per;
+            bc_ibm3_own(a, k, 1 + (int)(q >> 1), (q & 1) ? a.nx - 2 : 0, f);
+            continue;
+        }
+        r -= n_cols;  // the rest of the mask's box on those planes
+        const size_t per = (size_t)bh * bw;
+        const size_t q = r % per;
+        bc_ibm3_own(a, 2 + (int)(r / per), bi0 + (int)(q / bw), bj0 + (int)(q % bw), f);
+    }
+    if (!a.force) return;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) f[q] += __shfl_xor(f[q], off, kWave);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][q] = f[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int q = threadIdx.x;
+        const double s = ((part[0][q] + part[1][q]) + part[2][q]) + part[3][q];
+        if (s != 0.0) atomicAdd(a.force + q, s);  // a NaN is added too
+    }
+}
+
+// The vorticity vector of u, v, w from central differences (k_vorticity's
+// divisions by f32(2 d)), 0 on the six faces, NaN where mask != 0; mag =
+// sqrt((ox ox + oy oy) + oz oz); absmax <- nanmax(mag).  Null outputs are
+// not stored.
+__global__ __launch_bounds__(256) void k_vorticity3d(const float *__restrict__ u, const float *__restrict__ v,
+                                                     const float *__restrict__ w, const uint8_t *__restrict__ mask,
+                                                     float *__restrict__ ox, float *__restrict__ oy,
+                                                     float *__restrict__ oz, float *__restrict__ mag, float *absmax,
+                                                     int nz, int ny, int nx, float dx2, float dy2, float dz2) {
+    CFD_3D_INDEX
+    float m = 0.0f;
+    if (cell) {
+        float x = 0.0f, y = 0.0f, z = 0.0f, g = 0.0f;
+        if (mask && mask[c]) {
+            x = y = z = g = __builtin_nanf("");
+        } else if (interior3(k, j, i, nz, ny, nx)) {
+            x = (w[c + sy] - w[c - sy]) / dy2 - (v[c + sz] - v[c - sz]) / dz2;
+            y = (u[c + sz] - u[c - sz]) / dz2 - (w[c + 1] - w[c - 1]) / dx2;
+            z = (v[c + 1] - v[c - 1]) / dx2 - (u[c + sy] - u[c - sy]) / dy2;
+            g = sqrtf((x * x + y * y) + z * z);
+            if (g > m) m = g;  // a NaN never wins
+        }
+        if (ox) ox[c] = x;
+        if (oy) oy[c] = y;
+        if (oz) oz[c] = z;
+        if (mag) mag[c] = g;
+    }
+    if (absmax) wave_reduce_max_store(m, absmax);
 }
 
 // Mean of 0.5 ((u*u + v*v) + w*w) over n cells, then the three clips, in one
@@ -460,6 +617,67 @@ int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *o
     size_t nb = (n + 4095) / 4096;  // ~16 cells per thread
     if (nb > (size_t)kEnergy3Blocks) nb = kEnergy3Blocks;
     hipLaunchKernelGGL(k_energy_mean_clip3d, dim3((unsigned)nb), dim3(256), 0, s, u, v, w, n, out, lo, hi, slot);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y, const double *ibm_mask2d, int nz,
+                                   int ny, int nx, double y_max, double v_inf, int step, double force_strength,
+                                   int i0, int i1, int j0, int j1, double *force_out, void *stream) {
+    CFD_REQUIRE(u && v && w && y, "apply_channel_bc_ibm3d: null pointer");
+    CFD_REQUIRE(u != v && u != w && v != w, "apply_channel_bc_ibm3d: u, v, w must be three arrays");
+    CFD_SHAPE3D("apply_channel_bc_ibm3d", nz, ny, nx);
+    CFD_REQUIRE(i0 >= 0 && i0 <= i1 && i1 <= ny && j0 >= 0 && j0 <= j1 && j1 <= nx,
+                "apply_channel_bc_ibm3d: box [%d, %d) x [%d, %d) outside the (%d, %d) plane", i0, i1, j0, j1, ny, nx);
+    CFD_REQUIRE(!ibm_mask2d || (i0 < i1 && j0 < j1), "apply_channel_bc_ibm3d: empty box [%d, %d) x [%d, %d) with a mask",
+                i0, i1, j0, j1);
+    BcIbm3 a;
+    a.u = u;
+    a.v = v;
+    a.w = w;
+    a.y = y;
+    a.m = ibm_mask2d;
+    a.nz = nz;
+    a.ny = ny;
+    a.nx = nx;
+    a.y_max = y_max;
+    a.v_inf = v_inf;
+    a.step = step;
+    a.fs = force_strength;
+    a.i0 = i0;
+    a.i1 = i1;
+    a.j0 = j0;
+    a.j1 = j1;
+    a.force = force_out;
+    // the four ranges of owners (k_channel_bc_ibm3d)
+    const size_t mid = nz > 4 ? (size_t)(nz - 4) : 0, ex = (size_t)(nx - 1);
+    const int bi0 = i0 > 1 ? i0 : 1, bi1 = i1 < ny - 1 ? i1 : ny - 1;
+    const int bj0 = j0 > 1 ? j0 : 1, bj1 = j1 < nx - 2 ? j1 : nx - 2;
+    const int bh = bi1 > bi0 ? bi1 - bi0 : 0, bw = bj1 > bj0 ? bj1 - bj0 : 0;
+    const size_t n_plane = (size_t)ny * ex, n_rows = mid * 2 * ex, n_cols = mid * 2 * (size_t)(ny - 2);
+    const size_t n_box = ibm_mask2d ? mid * (size_t)bh * bw : 0;
+    size_t blocks = (n_plane + n_rows + n_cols + n_box + 255) / 256;
+    if (blocks > ((size_t)1 << 20)) blocks = (size_t)1 << 20;  // the kernel strides
+    hipLaunchKernelGGL(k_channel_bc_ibm3d, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a, n_plane, n_rows,
+                       n_cols, n_box, bi0, bj0, bh, bw);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_vorticity3d_f32(const float *u, const float *v, const float *w, const uint8_t *mask, float *ox, float *oy,
+                        float *oz, float *mag, float *absmax, int nz, int ny, int nx, double dx, double dy, double dz,
+                        void *stream) {
+    CFD_REQUIRE(u && v && w, "vorticity3d: null pointer");
+    CFD_REQUIRE(ox || oy || oz || mag || absmax, "vorticity3d: no output given");
+    float *out[4] = {ox, oy, oz, mag};
+    for (int o = 0; o < 4; ++o) {
+        if (!out[o]) continue;
+        CFD_REQUIRE(out[o] != u && out[o] != v && out[o] != w, "vorticity3d: outputs must not alias inputs");
+        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "vorticity3d: outputs must not alias each other");
+    }
+    CFD_SHAPE3D("vorticity3d", nz, ny, nx);
+    hipLaunchKernelGGL(k_vorticity3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, mask, ox, oy, oz,
+                       mag, absmax, nz, ny, nx, (float)(2.0 * dx), (float)(2.0 * dy), (float)(2.0 * dz));
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

@@ -26,6 +26,7 @@ __all__ = [
     "solve_pressure_gauss_seidel3d", "persistent_failures",
     "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
     "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
+    "apply_channel_bc_ibm3d", "compute_vorticity3d",
 ]
 
 
@@ -506,6 +507,49 @@ def apply_lid_bc3d(u, v, w, u_lid):
     nz, ny, nx = _fields3d(u, v=v, w=w)
     call("cfd_apply_lid_bc3d_f32", ptr(u), ptr(v), ptr(w), nz, ny, nx, float(np.float32(u_lid)), stream_handle())
     return u, v, w
+
+
+def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_strength, bbox=None, force_out=None):
+    """The cylinder channel's boundary conditions and immersed-boundary forcing
+    in place on (nz, ny, nx) float32 u, v, w, one launch
+    (cfd_apply_channel_bc_ibm3d_f32): inlet column (``y``: the float64 row
+    coordinates, ``step`` drives the perturbation), outlet copy, free-slip
+    spanwise faces, channel walls, then the factor 1 - m*force_strength where
+    the float64 (ny, nx) ``ibm_mask2d`` (None: no IBM) is positive, on every
+    plane.  ``bbox`` = (i0, i1, j0, j1): half-open rows and columns holding
+    every m > 0 (None: the whole plane); only that box is visited for the
+    forcing.  ``force_out``: optional float64 device tensor of 3 elements,
+    accumulated into (zero it first): the sums of before - after of u, v, w
+    over the forced cells.  Returns (u, v, w)."""
+    nz, ny, nx = _fields3d(u, v=v, w=w)
+    if y.dtype != torch.float64 or y.numel() != ny:
+        raise ValueError(f"y must be {ny} float64 row coordinates, got {tuple(y.shape)} {y.dtype}")
+    if ibm_mask2d is not None and (ibm_mask2d.dtype != torch.float64 or tuple(ibm_mask2d.shape) != (ny, nx)):
+        raise ValueError(f"ibm_mask2d must be a float64 ({ny}, {nx}) array, got {tuple(ibm_mask2d.shape)} "
+                         f"{ibm_mask2d.dtype}")
+    if force_out is not None and (force_out.dtype != torch.float64 or force_out.numel() != 3):
+        raise ValueError("force_out must be three float64 elements")
+    i0, i1, j0, j1 = (0, ny, 0, nx) if bbox is None else (int(b) for b in bbox)
+    call("cfd_apply_channel_bc_ibm3d_f32", ptr(u), ptr(v), ptr(w), ptr(y), ptr(ibm_mask2d), nz, ny, nx, float(y_max),
+         float(v_inf), int(step), float(force_strength), i0, i1, j0, j1, ptr(force_out), stream_handle())
+    return u, v, w
+
+
+def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax=None):
+    """The vorticity magnitude of (nz, ny, nx) float32 u, v, w
+    (cfd_vorticity3d_f32): central differences on the interior, 0 on the six
+    faces, NaN where the (nz, ny, nx) ``mask`` is set.  Returns mag, or
+    (ox, oy, oz, mag) with ``components=True``.  ``absmax``: optional zeroed
+    float32 device scalar that receives nanmax(mag) without a host sync."""
+    mag = torch.empty_like(u)
+    nz, ny, nx = _fields3d(u, v=v, w=w)
+    comp = [torch.empty_like(u) for _ in range(3)] if components else [None] * 3
+    if absmax is not None:
+        _f32(absmax, "absmax")
+    m = _mask_u8(mask, u.shape)
+    call("cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w), ptr(m), ptr(comp[0]), ptr(comp[1]),
+         ptr(comp[2]), ptr(mag), ptr(absmax), nz, ny, nx, float(dx), float(dy), float(dz), stream_handle())
+    return (comp[0], comp[1], comp[2], mag) if components else mag
 
 
 def persistent_failures(stream=None) -> int:

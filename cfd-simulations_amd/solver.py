@@ -20,6 +20,10 @@ arithmetic (tests/les_reference.py); parity with the reference is unpinned.
 pressure solves (the project's own generalisation: the reference is 2-D only).
 With a ``LesCavity3DConfig`` it runs the 3-D LES predictor
 (``K.predictor3d_fused_les``; pinned to tests/les3d_reference.py).
+``CylinderChannel3DSolver`` is that step on the cylinder channel extruded along
+z: channel boundary conditions with the immersed-boundary forcing in one
+kernel, the masked 3-D pressure solves, drag / lift and vorticity (pinned to
+tests/cyl3d_reference.py).
 
 Out of scope: plotting and video (OptimizedVisualizer),
 and HDF5 output (h5py is absent; ``save_snapshot`` writes the same layout to
@@ -563,7 +567,8 @@ class LidDrivenCavity3DSolver:
     dt reads the float64 mean of the previous step's nu_t together with
     max|V| in the same single host read.
 
-    Out of scope: snapshots, immersed boundaries or masks, float64, a
+    Out of scope: snapshots, immersed boundaries or masks (those:
+    CylinderChannel3DSolver), float64, a
     slab-decomposed (multi-GPU) step, and the 2-D step's clean_divergence
     stage (a v5 quirk with serial semantics that does not generalise)."""
 
@@ -707,8 +712,175 @@ class LidDrivenCavity3DSolver:
         return dt
 
 
+# ------------------------------------------------- 3-D cylinder channel
+@dataclass
+class CylinderChannel3DConfig(OptimizedTurbulentConfig):
+    """The v5 cylinder channel extruded along z: every v5 default kept (the
+    20 x 4 domain, the cylinder R = 0.5 at (4, 2), Re = 600, 600 x 180 cells,
+    red-black GS) plus nz, z_min, z_max and the derived dz; the cylinder's
+    axis is along z.  200 iterations per pressure solve, as in the 3-D cavity.
+    use_les=True forms the 3-D Smagorinsky eddy viscosity (constant 0.17)
+    inside the predictor; False (the default) ignores the constant.  float32
+    only."""
+    z_min: float = 0.0
+    z_max: float = 4.0
+    nz: int = 120
+    pressure_iterations: int = 200
+    smagorinsky_constant: float = 0.17
+    output_dir: str = "cylinder3d_re_600"
+    hdf5_file: str = "cylinder3d_re_600.h5"
+
+    def __post_init__(self):
+        super().__post_init__()
+        self.dz = (self.z_max - self.z_min) / (self.nz - 1)
+        if not self.memory_efficient:
+            raise ValueError("CylinderChannel3DConfig: the 3-D step is float32 only (memory_efficient=True)")
+
+
+def host_ibm_bbox(ibm):
+    """(i0, i1, j0, j1): the tight half-open box of rows and columns of the
+    2-D mask ``ibm`` that holds every ibm > 0; the whole grid if there is none."""
+    pos = np.asarray(ibm) > 0
+    ny, nx = pos.shape
+    rows, cols = np.flatnonzero(pos.any(axis=1)), np.flatnonzero(pos.any(axis=0))
+    if rows.size == 0:
+        return 0, ny, 0, nx
+    return int(rows[0]), int(rows[-1]) + 1, int(cols[0]), int(cols[-1]) + 1
+
+
+class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
+    """LidDrivenCavity3DSolver's projection step on the cylinder channel: the
+    v5 geometry extruded along z (host_grid / host_masks / host_potential_flow
+    on every plane, w = 0), fields (nz, ny, nx) float32 device tensors.
+
+    time_step is the cavity's with two stages exchanged.  The lid walls
+    become K.apply_channel_bc_ibm3d (inlet, outlet copy, free-slip spanwise
+    faces, channel walls and the immersed-boundary forcing with
+    force_strength = min(1, step / initial_steps), one launch, after the
+    predictor and after the projection; ``ibm_mask`` stays the 2-D float64
+    array and only its bounding box is visited).  The pressure solve takes the
+    solid mask: phi = zeros, then cfd_rbgs3d_f32 (use_fast_pressure, any
+    spacing) or cfd_jacobi3d_f32 (dx == dy == dz) with ``cylinder_mask``, the
+    2-D mask expanded once to (nz, ny, nx) uint8.  LES as in the cavity
+    solver.  No host synchronisation per step, except the adaptive dt's one
+    read from step 1000 on.
+
+    Forces: the second (post-projection) forcing call of each step adds the
+    momentum it removes, sum(before - after) of u, v, w over the forced cells
+    in float64, into that step's row of a device buffer; ``force_history`` and
+    ``force_coefficients()`` read it lazily.  ``compute_vorticity()`` returns
+    |omega| (NaN in the cylinder); with log_diagnostics ``diagnostics`` gains
+    ``vorticity_max`` of the step's final unclipped fields.
+
+    Not yet: temporal blocking of the masked 3-D solves (with a mask the
+    Jacobi runs single sweeps and the red-black GS in-place colour passes, so
+    the pressure solve dominates the step: DESIGN.md 4.4), periodic spanwise
+    boundaries, snapshots, float64 and the slab path."""
+
+    def __init__(self, config: CylinderChannel3DConfig):
+        super().__init__(config)
+        cfg = config
+        self.x, self.y, self.X, self.Y = host_grid(cfg)
+        self.z = np.linspace(cfg.z_min, cfg.z_max, cfg.nz)
+        self._y_dev = torch.from_numpy(self.y).to(self.device)
+        self.dist, cyl, ibm = host_masks(cfg, self.X, self.Y)
+        self.cylinder_mask_host, self.ibm_mask_host = cyl, ibm
+        self.ibm_mask = torch.from_numpy(ibm).to(self.device)
+        self.ibm_bbox = host_ibm_bbox(ibm)
+        self.cylinder_mask = (torch.from_numpy(cyl).to(self.device).to(torch.uint8)
+                              .expand(cfg.nz, cfg.ny, cfg.nx).contiguous())
+        u, v = host_potential_flow(cfg, self.X, self.Y, self.dist, ibm, np.float32)
+        self.u.copy_(torch.from_numpy(u).to(self.device).expand_as(self.u))
+        self.v.copy_(torch.from_numpy(v).to(self.device).expand_as(self.v))
+        self._force = torch.zeros((1024, 3), dtype=torch.float64, device=self.device)
+        self._dts = []
+
+    def solve_pressure_fast(self, div_u_star):
+        """phi = zeros, then the masked solve (with cfg.dt, like v5.py:328-347):
+        red-black GS on any spacing (use_fast_pressure), else the 7-point
+        Jacobi, which needs dx == dy == dz exactly.  Solid cells keep phi = 0."""
+        cfg = self.config
+        if not cfg.use_fast_pressure and not (cfg.dx == cfg.dy == cfg.dz):
+            raise ValueError(f"the 3-D Jacobi solve needs dx == dy == dz (got {cfg.dx}, {cfg.dy}, {cfg.dz}); "
+                             "use_fast_pressure=True takes any spacing")
+        self.phi.zero_()
+        if cfg.use_fast_pressure:
+            K.solve_pressure_gauss_seidel3d(self.phi, div_u_star, cfg.dx, cfg.dy, cfg.dz, cfg.dt, self.cylinder_mask,
+                                            cfg.pressure_iterations, cfg.pressure_tolerance, workspace=self._gs_ws,
+                                            iters_done=self._gs_done, phi_tmp=self._phi_tmp)
+        else:
+            K.solve_pressure_jacobi3d(self.phi, div_u_star, cfg.dx, cfg.dt, self.cylinder_mask,
+                                      cfg.pressure_iterations, phi_tmp=self._phi_tmp, rhs_ws=self._rhs_ws)
+        return self.phi
+
+    def _force_slot(self):
+        k = len(self._energy_steps)
+        if k >= self._force.shape[0]:
+            grown = torch.zeros((2 * self._force.shape[0], 3), dtype=torch.float64, device=self.device)
+            grown[:k] = self._force[:k]
+            self._force = grown
+        return self._force[k]
+
+    def apply_boundary_conditions(self, u, v, w):
+        """Channel BC + IBM forcing, one launch.  On the step's final fields
+        (the post-projection call) it also accumulates the step's force row
+        and, with log_diagnostics, takes max|omega| before the clips."""
+        cfg = self.config
+        final = u is self.u
+        K.apply_channel_bc_ibm3d(u, v, w, self._y_dev, self.ibm_mask, cfg.y_max, cfg.V_inf, self.step,
+                                 min(1.0, self.step / cfg.initial_steps), bbox=self.ibm_bbox,
+                                 force_out=self._force_slot() if final else None)
+        if final and cfg.log_diagnostics:
+            self._scal[3:4].zero_()
+            call("cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w), ptr(self.cylinder_mask), None, None, None, None,
+                 ptr(self._scal[3:4]), cfg.nz, cfg.ny, cfg.nx, float(cfg.dx), float(cfg.dy), float(cfg.dz),
+                 stream_handle())
+
+    def time_step(self):
+        dt = super().time_step()
+        self._dts.append(float(dt))
+        return dt
+
+    def compute_vorticity(self):
+        """|omega| of the current fields: 0 on the six faces, NaN in the cylinder."""
+        cfg = self.config
+        return K.compute_vorticity3d(self.u, self.v, self.w, cfg.dx, cfg.dy, cfg.dz, mask=self.cylinder_mask)
+
+    @property
+    def diagnostics(self):
+        """The cavity solver's values plus ``vorticity_max``, nanmax|omega| of
+        the last step's fields before the clips (log_diagnostics=True)."""
+        d = LidDrivenCavity3DSolver.diagnostics.fget(self)
+        d["vorticity_max"] = float(self._scal[3].item())
+        return d
+
+    @property
+    def force_history(self):
+        """[(step, Fx, Fy, Fz)]: per step, the sums of before - after of u, v,
+        w over the cells the post-projection forcing changed (float64), read
+        lazily from the device."""
+        n = len(self._energy_steps)
+        vals = self._force[:n].cpu().numpy() if n else np.zeros((0, 3))
+        return [(s, float(f[0]), float(f[1]), float(f[2])) for s, f in zip(self._energy_steps, vals)]
+
+    def force_coefficients(self):
+        """[(step, Cd, Cl)] from force_history: C = 2 F dx dy dz / (dt V_inf^2
+        2R (z_max - z_min)) with F = Fx (drag) or Fy (lift) and the step's own
+        dt -- the momentum the forcing removed per unit time over the dynamic
+        pressure times the cylinder's frontal area."""
+        cfg = self.config
+        vol = cfg.dx * cfg.dy * cfg.dz
+        area = 2.0 * cfg.R_cylinder * (cfg.z_max - cfg.z_min)
+        out = []
+        for (s, fx, fy, _), dt in zip(self.force_history, self._dts):
+            k = 2.0 * vol / (dt * cfg.V_inf ** 2 * area)
+            out.append((s, k * fx, k * fy))
+        return out
+
+
 def monitor_simulation_health3d(solver: LidDrivenCavity3DSolver, step: int) -> bool:
-    """monitor_simulation_health's thresholds (v5.py:599-613) on u, v, w:
+    """monitor_simulation_health's thresholds (v5.py:599-613) on u, v, w
+    (LidDrivenCavity3DSolver or CylinderChannel3DSolver):
     non-finite values, max|V| > max_velocity, max|div| above 20 (step <= 1000)
     or 2 (after); device reductions with one host read."""
     cfg = solver.config

@@ -433,6 +433,48 @@ int cfd_apply_lid_bc3d_f32(float *u, float *v, float *w, int nz, int ny, int nx,
  * slot per (device, stream) in use: up to 32 streams per device. */
 int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *out,
                                float lo, float hi, void *stream);
+/* Channel boundary conditions and immersed-boundary forcing of the 3-D
+ * cylinder channel (cylinder axis along z) on u, v, w in one launch: the
+ * project's own 3-D form of apply_boundary_conditions (v5.py:349-360)
+ * followed by apply_ibm_fast (v5.py:228-237).  Net effect, in the order of
+ * these assignments:
+ *   1. inlet x = 0, all k and i: u = f32(v_inf*(1 + pert(y[i], step))) with
+ *      pert as cfd_apply_bc2d_f32 forms it (double arithmetic), v = w = 0;
+ *   2. outlet: f[:, :, nx-1] = f[:, :, nx-2] for u, v, w;
+ *   3. free-slip spanwise faces, whole planes: u[0] = u[1], v[0] = v[1],
+ *      w[0] = 0, likewise plane nz-1 from nz-2;
+ *   4. channel walls i = 0 and i = ny-1, all k and j: u = v = w = 0 (written
+ *      last: the walls own their edges);
+ *   5. on every cell with m = ibm_mask2d[i, j] > 0, boundary cells included:
+ *      f = (float)((double)f * (1.0 - m*force_strength)) for u, v, w.
+ * ibm_mask2d: the float64 (ny, nx) mask, used for every plane (NULL: no IBM).
+ * [i0, i1) x [j0, j1): rows and columns that contain every m > 0; only that
+ * box (times all planes) is visited for step 5 and the mask is read inside it
+ * only, so the stage costs its faces plus the box.  0, ny, 0, nx is always
+ * valid and any covering box gives the same bits.  A box outside the grid,
+ * or an empty one with a mask, is CFD_E_INVALID.  force_out (optional device
+ * double[3], zeroed by the caller, accumulated into with float64 atomics):
+ * the sums of (double)before - (double)after of u, v and w over the cells
+ * with m > 0, before being the value after steps 1-4; the order of the sum
+ * is not fixed.  Every cell is written by exactly one thread, and no thread
+ * reads a cell another one writes: the thread that owns a copy's source
+ * (column nx-2, planes 1 and nz-2) writes the copies.  y: device double[ny].
+ * u, v, w must be three arrays; every dimension >= 3. */
+int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y,
+                                   const double *ibm_mask2d, int nz, int ny, int nx, double y_max,
+                                   double v_inf, int step, double force_strength, int i0, int i1,
+                                   int j0, int j1, double *force_out, void *stream);
+/* The vorticity of u, v, w from central differences, with dx2 = f32(2*dx)
+ * (likewise dy2, dz2) and the divisions of cfd_vorticity2d_f32:
+ *   ox = (wN - wS)/dy2 - (vU - vD)/dz2,  oy = (uU - uD)/dz2 - (wE - wW)/dx2,
+ *   oz = (vE - vW)/dx2 - (uN - uS)/dy2,  mag = sqrt((ox*ox + oy*oy) + oz*oz)
+ * on the interior, 0 on the six faces, NaN where mask != 0 (mask: (nz, ny, nx)
+ * uint8, may be NULL).  Each of ox, oy, oz, mag may be NULL (not stored);
+ * absmax (optional device float*, zeroed by the caller) receives nanmax(mag).
+ * At least one of the five must be given; outputs alias nothing. */
+int cfd_vorticity3d_f32(const float *u, const float *v, const float *w, const uint8_t *mask,
+                        float *ox, float *oy, float *oz, float *mag, float *absmax,
+                        int nz, int ny, int nx, double dx, double dy, double dz, void *stream);
 
 /* --------------------------------------------------- float64 fields */
 /* memory_efficient=False (v5.py:287-296): every field float64; the kernels

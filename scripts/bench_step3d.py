@@ -26,6 +26,12 @@ time_step, always at 512^3 whatever --sizes says (--no-step skips it).  With
 --check: the fused LES march at the largest size on the same sample of planes
 against tests/les3d_reference.py, bit for bit.
 
+--cylinder: the 3-D cylinder channel leg instead, at the
+default 600 x 180 x 120 grid: cfd_apply_channel_bc_ibm3d_f32 with the mask's
+tight box and with the whole-grid box and cfd_vorticity3d_f32 (ms, algorithmic
+bytes and the fraction of the HBM peak), then CylinderChannel3DSolver.time_step
+with the red-black GS, LES off and on, with the pressure solve's share of it.
+
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
 `--les --sizes 512 --no-step`, `--les --sizes 1024 --no-step --check`, then
@@ -283,6 +289,99 @@ def time_step_cfg(s, n, iters, steps, label):
                       "energy_last": s.energy_history[-1][1]}), flush=True)
 
 
+def window_ms(fn, launches):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / launches
+
+
+def bc_ibm_bytes(nz, ny, nx, ibm, bbox):
+    """Algorithmic bytes of one cfd_apply_channel_bc_ibm3d_f32 call: 12 B (u, v,
+    w) per cell read or written once, the mask's box read once (8 B per cell)."""
+    i0, i1, j0, j1 = bbox
+    inner = (ny - 2) * (nx - 2)                      # a plane without walls, inlet and outlet columns
+    rd = 2 * inner + (nz - 4) * (ny - 2)             # planes 1 and nz-2; the outlet's source column between them
+    wr = 2 * ny * nx                                 # planes 0 and nz-1
+    wr += (nz - 2) * (2 * nx + 2 * (ny - 2))         # wall rows, inlet and outlet columns of the other planes
+    forced = int((ibm[1:-1, 1:-2] > 0).sum())        # forced cells not counted above: read and written
+    rd += (nz - 4) * forced
+    wr += (nz - 2) * forced
+    return 12 * (rd + wr) + 8 * (i1 - i0) * (j1 - j0)
+
+
+def cylinder_leg(rounds, launches, steps):
+    """The 3-D cylinder channel at its default 600 x 180 x 120 grid (DESIGN.md
+    4.4): the BC + IBM stage with the mask's tight box and with the whole-grid
+    box, the vorticity kernel, and time_step with RB-GS, LES off and on, with
+    the pressure solve's share of the step (the library's solve timing)."""
+    from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
+    c = CylinderChannel3DConfig()
+    s = CylinderChannel3DSolver(c)
+    nz, ny, nx = c.nz, c.ny, c.nx
+    cells = nz * ny * nx
+    whole = (0, ny, 0, nx)
+    force = torch.zeros(3, dtype=torch.float64, device="cuda")
+    mag = torch.empty_like(s.u)
+
+    def bc(bbox):
+        K.apply_channel_bc_ibm3d(s.u, s.v, s.w, s._y_dev, s.ibm_mask, c.y_max, c.V_inf, 1500, 1e-3, bbox=bbox,
+                                 force_out=force)
+
+    def vort():
+        call("cfd_vorticity3d_f32", _lib.ptr(s.u), _lib.ptr(s.v), _lib.ptr(s.w), _lib.ptr(s.cylinder_mask), None,
+             None, None, _lib.ptr(mag), None, nz, ny, nx, c.dx, c.dy, c.dz, _lib.stream_handle())
+
+    cases = {"bc_ibm_tight_box": (lambda: bc(s.ibm_bbox), bc_ibm_bytes(nz, ny, nx, s.ibm_mask_host, s.ibm_bbox)),
+             "bc_ibm_whole_box": (lambda: bc(whole), bc_ibm_bytes(nz, ny, nx, s.ibm_mask_host, whole)),
+             "vorticity3d": (vort, 17 * cells)}      # u, v, w and the mask read, |omega| written
+    ms = {k: [] for k in cases}
+    for fn, _ in cases.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, (fn, _) in cases.items():
+            ms[k].append(window_ms(fn, launches))
+    i0, i1, j0, j1 = s.ibm_bbox
+    for k, v in ms.items():
+        med, nbytes = statistics.median(v), cases[k][1]
+        print(json.dumps({"bench": "cylinder3d_kernel", "grid": [nz, ny, nx], "kernel": k, "ms": round(med, 4),
+                          "ms_min": round(min(v), 4), "ms_max": round(max(v), 4), "rounds": rounds,
+                          "launches_per_round": launches, "ibm_box": [i0, i1, j0, j1],
+                          "box_fraction_of_plane": round((i1 - i0) * (j1 - j0) / (ny * nx), 4),
+                          "algorithmic_bytes": nbytes, "full_pass_bytes": 24 * cells + 8 * ny * nx,
+                          "hbm_fraction": round(nbytes / (med * 1e-3) / HBM_PEAK, 4)}), flush=True)
+    del s, mag
+    torch.cuda.empty_cache()
+    ms_solve, n_sweeps = ctypes.c_double(0), ctypes.c_longlong(0)
+    for les in (False, True):
+        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=les))
+        for _ in range(2):
+            s.time_step()
+        torch.cuda.synchronize()
+        ms_step = window_ms(s.time_step, steps)
+        # the solve's share: the same steps again with the library's event pairs around every solve
+        call("cfd_timing_enable", 1)
+        call("cfd_timing_read", ctypes.byref(ms_solve), ctypes.byref(n_sweeps), 1)
+        for _ in range(steps):
+            s.time_step()
+        call("cfd_timing_read", ctypes.byref(ms_solve), ctypes.byref(n_sweeps), 1)
+        call("cfd_timing_enable", 0)
+        f = s.force_coefficients()[-1]
+        print(json.dumps({"bench": "cylinder3d_time_step", "grid": [nz, ny, nx], "les": les, "pressure": "rbgs",
+                          "iterations": c.pressure_iterations, "steps": steps, "ms_per_step": round(ms_step, 3),
+                          "solve_ms_per_step": round(ms_solve.value / steps, 3),
+                          "solve_share": round(ms_solve.value / steps / ms_step, 3),
+                          "gcell_per_s": round(cells / ms_step / 1e6, 3), "energy_last": s.energy_history[-1][1],
+                          "cd_last": f[1], "cl_last": f[2]}), flush=True)
+        del s
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="512,1024")
@@ -294,9 +393,13 @@ def main():
     ap.add_argument("--pmc-run", choices=["march", "percell"])
     ap.add_argument("--les", action="store_true", help="the LES leg (see above) instead of the scalar-nu one")
     ap.add_argument("--step-only", action="store_true", help="with --les: only the two 512^3 time_step timings")
+    ap.add_argument("--cylinder", action="store_true", help="the 3-D cylinder channel leg (see above) and nothing else")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_step3d.py needs the GPU")
+    if a.cylinder:
+        cylinder_leg(a.rounds, a.launches, 3)
+        return
     if a.les:
         sizes = [] if a.step_only else [int(s) for s in a.sizes.split(",")]
         bad = 0
