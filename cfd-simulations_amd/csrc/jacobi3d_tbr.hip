@@ -94,6 +94,12 @@ constexpr int kStoreNt = 2;
 #ifndef CFD_TBR_EARLY
 #define CFD_TBR_EARLY 1
 #endif
+#ifndef CFD_TBR_ROT3  // K = 4 Jacobi: level queues rotated with period 3 (see jacobi3d_tbr)
+#define CFD_TBR_ROT3 1
+#endif
+#ifndef CFD_TBR_V1  // ROT3: level 0 lives in the slot ring only (see the DMA row wave)
+#define CFD_TBR_V1 1
+#endif
 
 
 __device__ inline float4 ldb4(__amdgpu_buffer_rsrc_t r, uint32_t byte_ofs) {
@@ -235,6 +241,8 @@ __device__ inline float4 level4(float4 c, float wl, float er, float4 N, float4 S
     // element the scalar operation, in the single sweep's order), written
     // out so that the pairs are the aligned register pairs of the float4s
     typedef float v2 __attribute__((ext_vector_type(2)));
+    // (E + W as four single adds, no pairs built, is the same bits but 4 more
+    // VALU per step and 8 more VGPRs in the K = 4 row wave: not taken)
     const v2 mid = {c.y, c.z};  // E of cells 0, 1 and W of cells 2, 3
     v2 s01 = mid + v2{wl, c.x};
     v2 s23 = v2{c.w, er} + mid;
@@ -279,6 +287,14 @@ struct P4 {
 __device__ inline v2f_t pick2(const P4 &f, int h) { return h ? f.o : f.e; }
 __device__ inline P4 split4(float4 f) { return P4{v2f_t{f.x, f.z}, v2f_t{f.y, f.w}}; }
 
+// a float4 of unspecified (but not undefined) contents, for a value nobody reads
+// (an empty asm that "writes" it: no instruction, and no constant for the
+// compiler to materialise on the other path)
+__device__ inline float4 any4() {
+    gv4f v;
+    asm volatile("" : "=v"(v));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 // Jacobi register-queue entry as two 64-bit values (CFD_TBR_Q64): a float4
 // held this way is copied by two v_mov_b64 when its queue shifts, where the
 // float4's four 32-bit components were copied one v_mov_b32 at a time
@@ -668,7 +684,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     const bool xin = x < nx;
     const size_t plane = (size_t)ny * nx;
     const int zs = z0 - K + 1;  // first front plane
-    // last front plane; the LDS-DMA march runs whole groups of 6 steps (the
+    // last front plane; the rotated LDS-DMA march runs whole groups of PER steps (the
     // extra steps at the end compute planes past the chunk and store nothing)
     const int zl0 = z1 + K - 2;
     // register queues rotated by compile-time slots (see the DMA row wave) up
@@ -677,11 +693,21 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     // with them at 2 rows per wave); K = 4 spills with them (r03: 111 VGPRs
     // for the Jacobi, 34 for the GS -- although the shifting queues' moves are
     // about half of the K = 4 passes' VALU instructions)
-    constexpr bool ROT = DMA && K <= 3 && (MODE == kJacobi || RPW <= 2) && !SHIFTQ;
+    // ROT3 (the K = 4 Jacobi at 2 rows per wave, on T0S with the rhs by
+    // register loads): nothing in its step depends on the even/odd parity --
+    // level 0 comes from the slot ring, itself of period 3 -- so its march is
+    // unrolled by 3, not 6: V and the level queues take compile-time slots
+    // (72 of the 96 v_mov_b64 per two steps gone), Rq keeps shifting, and the
+    // loop body is half the 6-step one that spilled.  It fits 168 VGPRs
+    // without scratch only with V1 and any4() (see the DMA row wave): 159.
+    // r07, 1024^3: VALU per step and full-work wave 301 -> 243, pass -2 %.
+    constexpr bool ROT3 = T0S && K == 4 && RPW == 2 && !RDMA && !SHIFTQ && CFD_TBR_ROT3;
+    constexpr bool ROT = (DMA && K <= 3 && (MODE == kJacobi || RPW <= 2) && !SHIFTQ) || ROT3;
     // (a K = 4 Jacobi with its rhs queue rotated with period 4 -- a march
     // unrolled by 4 -- spilled 22 VGPRs and took 4.96-5.04 ms per pass against
     // 2.71, r04: removed in r05)
-    const int zl = ROT ? zs + 6 * ((zl0 - zs + 6) / 6) - 1 : zl0;
+    constexpr int PER = ROT3 ? 3 : 6;  // the rotated march's period: whole groups of PER steps
+    const int zl = ROT ? zs + PER * ((zl0 - zs + PER) / PER) - 1 : zl0;
     auto P = [&](int p) { return a.in + (size_t)p * plane; };
     auto fixedp = [&](int p) { return (p == a.zb - 1 && a.fixed_lo) || (p == a.ze && a.fixed_hi); };
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -741,6 +767,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 else
                     return f;
             };
+            // V1 (ROT3): level 1 takes its own row of planes z and z + 1 from
+            // the slots they sit in (one more ds_read_b128 per row and step) and
+            // only plane z - 1 is carried, in V[j][0]: 16 VGPRs fewer, which is
+            // what lets the rotated queues fit without scratch
+            constexpr bool V1 = ROT3 && CFD_TBR_V1;
             VT V[RPW][3], Rq[RPW][K];
             QQ Q[RPW][K][3];
             float4 Rn[RPW];  // !RDMA: the rhs row of the next step's plane, in flight
@@ -787,9 +818,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 for (int l = 0; l < K; ++l) Q[j][l][0] = Q[j][l][1] = Q[j][l][2] = QQ{};
                 // planes zs - 1 and zs in slots 2 and 0 (slot (q - zs) mod 3), or 0
                 // and 1 (shifted queues)
-                V[j][ROT ? 2 : 0] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs - 1, nz, plane), bo[j]));
-                V[j][ROT ? 0 : 1] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs, nz, plane), bo[j]));
-                V[j][ROT ? 1 : 2] = toV(z4);
+                V[j][V1 ? 0 : ROT ? 2 : 0] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs - 1, nz, plane), bo[j]));
+                if constexpr (!V1) {
+                    V[j][ROT ? 0 : 1] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs, nz, plane), bo[j]));
+                    V[j][ROT ? 1 : 2] = toV(z4);
+                }
                 // rhs rows of planes before zs only feed levels of planes below the
                 // ones the outputs need (the pipeline fill), so they start at 0
 #pragma unroll
@@ -830,7 +863,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             // period 6 is a multiple of K) the rhs of plane q in slot
             // (q - zs) mod K of Rq; the march is unrolled by 6 so that every
             // slot index is a compile-time constant.  (K = 4 shifts Rq.)
-            constexpr bool ROTR = ROT && 6 % K == 0;
+            constexpr bool ROTR = ROT && PER % K == 0;
             // memory operations per step and wave, for EARLY's vmcnt wait:
             // staging DMAs, !RDMA rhs loads, level-K stores (one per row, issued
             // for every row: see phase R), first-pass rhs stores
@@ -1016,6 +1049,8 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 for (int j = 0; j < RPW; ++j) {
                     if constexpr (MODE == kRbgs)
                         V[j][vs(1)] = ldsp(pr + (rr[j] - 1) * 256 + 4 * lane);
+                    else if constexpr (V1)
+                        ;  // (read where level 1 uses it)
                     else if constexpr (LB && T0S)
                         V[j][vs(1)] = toV(ZERO ? z4 : lds4l(lds_ptr(bSn) + (1 + j * NWR) * RS));
                     else if constexpr (LB)
@@ -1108,6 +1143,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                         o.er = up(l - 1, j * NWR)[260];
                         o.N = lds4l(tp(l - 1, j * NWR + 1));
                         o.S = lds4l(tp(l - 1, j * NWR - 1));
+                        // (the compiler sinks the N and S reads into the `upd`
+                        // block below the DPP moves: two LDS round trips per
+                        // update.  Pinned up here with the x-halo reads, one round
+                        // trip: 1756.5 against 1754.7 Gcell/s at 1024^3, inside the
+                        // runs' spread -- r07, not kept)
                     } else {
                         o.wl = row[3];
                         o.er = row[260];
@@ -1185,11 +1225,22 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                 __builtin_amdgcn_raw_buffer_store_b128(vv, ro, (int)so[j], 0, kStoreNt);
                             }
                           }
-                        } else if (r >= l && r < NR - l) {
+                        } else if ((ROT3 && l == 1) || (r >= l && r < NR - l)) {  // (level 1: every row)
                             // level l-1 at planes p (c), p + 1 (U), p - 1 (D)
-                            const float4 c = f4_of(l == 1 ? V[j][vs(0)] : Q[j][l - 1][qs(l - 1, 1)]);
-                            const float4 U = f4_of(l == 1 ? V[j][vs(1)] : Q[j][l - 1][qs(l - 1, 2)]);
-                            const float4 D = f4_of(l == 1 ? V[j][vs(-1)] : Q[j][l - 1][qs(l - 1, 0)]);
+                            float4 c, U, D;
+                            if constexpr (V1) {
+                                if (l == 1) {  // planes z, z + 1 from their slots, z - 1 carried
+                                    c = ZERO ? z4 : lds4l(tp(0, j * NWR));
+                                    U = ZERO ? z4 : lds4l(lds_ptr(bSn) + (1 + j * NWR) * RS);
+                                    D = f4_of(V[j][0]);
+                                    V[j][0] = toV(c);
+                                }
+                            }
+                            if (!V1 || l > 1) {
+                                c = f4_of(l == 1 ? V[j][vs(0)] : Q[j][l - 1][qs(l - 1, 1)]);
+                                U = f4_of(l == 1 ? V[j][vs(1)] : Q[j][l - 1][qs(l - 1, 2)]);
+                                D = f4_of(l == 1 ? V[j][vs(-1)] : Q[j][l - 1][qs(l - 1, 0)]);
+                            }
                             const LdsIn in = fetch(l, j);
                             // (lanes 0 / 63: the x-halo cells, as the GS branch)
                             const float wl = dpp_from_lower_old(in.wl, c.w);
@@ -1222,6 +1273,13 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                 const gv4f vv = {v.x, v.y, v.z, v.w};
                                 __builtin_amdgcn_raw_buffer_store_b128(vv, ro, (int)so[j], 0, kStoreNt);
                             }
+                        } else if constexpr (ROT3) {
+                            // a row outside level l's range: nothing reads its slot
+                            // (phase W and the levels above skip the row too), so it
+                            // need not keep its old value either -- without this the
+                            // join of the two paths cost the hot one a copy of the old
+                            // value before the branch and one of the new value after
+                            if (l < K) Q[j][l][sl3(R - l + 1)] = toV(any4());
                         }
                         if (EARLY && l == K && !(r >= l && r < NR - l)) {
                             // a row outside level K's range still issues its store
@@ -1268,6 +1326,15 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                     for (int zb = zs; zb <= zl; zb += 2) {
                         step(zb, I0{}, I0{}, bpc);
                         if (zb + 1 <= zl) step(zb + 1, I1{}, I0{}, bpc);
+                    }
+                    return;
+                }
+                if constexpr (ROT3) {
+                    // zl - zs + 1 is a multiple of 3; the parity is unused (see ROT3)
+                    for (int zb = zs; zb <= zl; zb += 3) {
+                        step(zb, I0{}, std::integral_constant<int, 0>{}, bpc);
+                        step(zb + 1, I0{}, std::integral_constant<int, 1>{}, bpc);
+                        step(zb + 2, I0{}, std::integral_constant<int, 2>{}, bpc);
                     }
                     return;
                 }
@@ -1544,8 +1611,12 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
         const char *e = getenv("CFD_TBR_SHIFTQ");
         return e && atoi(e) == 1;
     }();
-    const bool shiftq = MODE == kJacobi && pd == 1 && best->K == 3 &&
-                        (shiftq_all || (nsteps % 6 != 0 && nsteps < 216));
+    // (4, 11, 2) rotates with period 3 (ROT3): 1 or 2 extra steps, which the
+    // 2 % it saves per step (r07, 1024^3) repays from 48 steps per extra one on
+    const int extra3 = (3 - nsteps % 3) % 3;
+    const bool shiftq = MODE == kJacobi && pd == 1 &&
+                        ((best->K == 3 && (shiftq_all || (nsteps % 6 != 0 && nsteps < 216))) ||
+                         (best->K == 4 && (shiftq_all || nsteps < 48 * extra3)));
 #define CFD_TBR_L(KV, NW, RP, PR, PDV) \
     hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, PR, PDV, MODE>), dim3(blocks), dim3((NW + 1) * 64), 0, s, a)
 #define CFD_TBR(KV, NW, RP)                                                                   \
@@ -1562,7 +1633,7 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
     // also with shifting queues
 #define CFD_TBRF(KV, NW, RP)                                                                 \
     do {                                                                                     \
-        if constexpr (MODE == kJacobi && KV == 3) {                                          \
+        if constexpr (MODE == kJacobi && (KV == 3 || KV == 4)) {                             \
             if (shiftq) {                                                                    \
                 if (first == (kFirstRhs | kFirstZero))                                       \
                     hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kFirstRhs | kFirstZero, true>), \
