@@ -146,11 +146,14 @@ int jacobi2d_tbk_pass(int K, const T *in, T *out, const T *div, const uint8_t *m
 struct RbgsWs;
 struct RbgsConsts;
 // (levels half-sweeps from half-sweep h0; rollback = half-sweeps per pass of
-// the solve, nhalf = its half-sweeps in all: see jacobi3d_tbr.hip)
+// the solve, nhalf = its half-sweeps in all: see jacobi3d_tbr.hip; mask2d: an
+// optional (ny, nx) solid mask applied to every plane, for the depths and
+// rows rbgs3d_tbr_mask_ok accepts)
 int rbgs3d_tbr_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
                     int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
                     int levels, RbgsWs *ws, int rollback, int nhalf, int rows, hipStream_t s,
-                    int lag = 0);
+                    int lag = 0, const uint8_t *mask2d = nullptr);
+bool rbgs3d_tbr_mask_ok(int levels, int rows);
 // red-black GS workspace (cfd_rbgs_workspace_bytes): flags[0] = iterations,
 // flags[1] = iterations done, flags[2] = tolerance (float bits), float
 // maxc[iterations] at byte 16, then the small-grid 2-D kernel's 16 slot rows
@@ -195,10 +198,11 @@ RbgsConsts rbgs3d_consts(double dx, double dy, double dz, float dt, double toler
 // whether the fused out-of-place pass applies (no mask, float4 layout, blocking on)
 bool rbgs3d_fused_ok(const float *phi, const float *phi_tmp, const float *div, const uint8_t *mask,
                      int nx);
-// in-place colour pass over planes [z0, z1); local plane 0 = global plane zoff
+// in-place colour pass over planes [z0, z1); local plane 0 = global plane zoff;
+// mask2d: `mask` is (ny, nx) and applies to every plane (else (nz, ny, nx))
 int rbgs3d_colour_pass(int colour, float *phi, const float *div, const uint8_t *mask, int ny,
                        int nx, int z0, int z1, int zoff, const RbgsConsts &k, RbgsWs *ws, int it,
-                       hipStream_t s);
+                       hipStream_t s, bool mask2d = false);
 int rbgs3d_iters_per_pass();  // slab solves: 1, or 2 (blocking depth 4)
 int rbgs3d_half_per_pass();   // single-GPU solves: half-sweeps per pass, 2..4 (auto 4)
 int rbgs3d_fused_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
@@ -206,5 +210,5 @@ int rbgs3d_fused_pass(const float *in, float *out, const float *div, int nz, int
                       int iters, RbgsWs *ws, hipStream_t s, int lag = 0);
 int rbgs3d_half_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
                      int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
-                     int levels, RbgsWs *ws, hipStream_t s, int lag);
+                     int levels, RbgsWs *ws, hipStream_t s, int lag, const uint8_t *mask2d = nullptr);
 }  // namespace cfd

@@ -97,6 +97,9 @@ constexpr int kStoreNt = 2;
 #ifndef CFD_TBR_ROT3  // K = 4 Jacobi: level queues rotated with period 3 (see jacobi3d_tbr)
 #define CFD_TBR_ROT3 1
 #endif
+#ifndef CFD_TBR_MSTEP  // kMask2d: the mask tests formed per z-step (see the DMA row wave)
+#define CFD_TBR_MSTEP 1
+#endif
 #ifndef CFD_TBR_V1  // ROT3: level 0 lives in the slot ring only (see the DMA row wave)
 #define CFD_TBR_V1 1
 #endif
@@ -139,7 +142,13 @@ struct TbrArgs {
     int nhalf;       // GS rollback: half-sweeps the solve scheduled (2 x iterations)
     const int *count;  // GS rollback: iterations done (device)
     int lag;         // GS: the stop test reads maxc[it-1-lag], maxc[it-2-lag] (see rbgs3d_tbr_pass)
-    float *rhs_out;  // first pass (F & kFirstRhs): the rhs of the owned cells goes here
+    // One slot for two pointers no launch has both of (the struct keeps its
+    // size: a larger one, passed by value to the called halo wave, changed the
+    // stack frame and LDS layout of the Jacobi first-pass kernels that call it)
+    union {
+        float *rhs_out;         // Jacobi first pass (F & kFirstRhs): the rhs of the owned cells goes here
+        const uint8_t *mask2d;  // GS, F & kMask2d: the z-invariant solid mask (ny, nx), nonzero = solid
+    };
     int xbw;         // XCD block width in x-segments (0: each XCD takes whole tile rows), see tbr_launch
     unsigned long long *trace;  // diagnostics (cfd_set_tbr_trace): per-wave step timestamps, or NULL
 };
@@ -170,16 +179,32 @@ __device__ inline void trace_mark(unsigned long long *tr, int wave, int step, in
 // for the later passes, replacing the separate RHS prologue;
 // kFirstZero: level 0 is phi = 0 (v5.py:337's zero fill): nothing is read
 // from `in`, so the pass can write either buffer and no memset is needed.
-enum { kFirstRhs = 1, kFirstZero = 2 };
+// kMask2d (red-black GS on the LDS-DMA path): a solid mask (ny, nx), the same
+// in every plane (TbrArgs::mask2d).  A wave keeps its rows and columns for its
+// whole z-march, so the mask bits of the cells it computes are constants of
+// the march: loaded once per tile (mask4), held in one VGPR, one select per
+// updated cell.  A solid cell keeps the value of the level below at every
+// level (the oracle's `if (mask[c]) continue;`) and folds |C - C| = 0 into
+// max|change|; every owner of a cell -- the row waves over the tile's halo
+// rows, the halo wave over the x-halo chunks -- applies it, so the copies
+// neighbouring tiles recompute stay the same.
+enum { kFirstRhs = 1, kFirstZero = 2, kMask2d = 4 };
+// the mask bytes of 4 cells at byte offset ofs of the (ny, nx) mask (kOob: 0)
+__device__ inline uint32_t mask4(const TbrArgs &a, uint32_t ofs) {
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t *>(a.mask2d), (short)0, (int)((size_t)a.ny * a.nx), 0x00020000);
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)ofs, 0, 0);
+}
 
 // One level on the float4 of cells x .. x+3.  Jacobi: every interior cell.
 // Red-black GS: the cells of colour `par` parity (v5.py:213-219 generalised:
 // (((cx(E+W) + cy(N+S)) + cz(U+D)) - rhs) * cd with rhs = -div * dt_inv, the
 // in-place kernel's operation order); `chg` folds max|change| of own cells.
-template <int MODE, bool PRE, bool PK = false>
+// MSK: m4 holds the cells' mask bytes (kMask2d); a solid cell keeps its value.
+template <int MODE, bool PRE, bool PK = false, bool MSK = false>
 __device__ inline float4 level4(float4 c, float wl, float er, float4 N, float4 S, float4 U,
                                 float4 D, float4 d, int x, int nx, bool upd, const TbrArgs &a,
-                                int par, bool own, float &chg) {
+                                int par, bool own, float &chg, uint32_t m4 = 0) {
     if (!upd) return c;
     if (MODE == kRbgs) {
         // x % 4 == 0, so the colour updates cells k = par & 1 and k + 2 of the
@@ -205,6 +230,11 @@ __device__ inline float4 level4(float4 c, float wl, float er, float4 N, float4 S
         const int x0 = x + (hi ? 1 : 0);  // the pair's cells x0, x0 + 2 (x0 + 2 >= 2)
         o.x = (x0 != 0 && x0 != nx - 1) ? o.x : C.x;
         o.y = (x0 + 2 != nx - 1) ? o.y : C.y;
+        if constexpr (MSK) {  // bytes hi, hi + 2 of m4
+            const uint32_t mb = hi ? m4 >> 8 : m4;
+            o.x = (mb & 0xffu) ? C.x : o.x;
+            o.y = (mb & 0xff0000u) ? C.y : o.y;
+        }
         if (own) {  // fmaxf ignores a NaN change like the `ch > mx` test
             chg = fmaxf(chg, fabsf(o.x - C.x));
             chg = fmaxf(chg, fabsf(o.y - C.y));
@@ -354,9 +384,11 @@ __device__ inline GsPk gs_pk(const TbrArgs &a) {
     asm volatile("" : "+v"(k.cx), "+v"(k.cy), "+v"(k.cz), "+v"(k.cd), "+v"(k.ndt));
     return k;
 }
+// MSK: bits mb, mb + 2 of mk are the solid bits of the pair's cells (kMask2d).
+template <bool MSK = false>
 __device__ inline v2f_t level2(v2f_t C, v2f_t O, float wl, float er, v2f_t N, v2f_t S, v2f_t U, v2f_t D,
                                v2f_t rhs, int h, int x, int nx, bool upd, const GsPk &a, bool own,
-                               float &chg) {
+                               float &chg, uint32_t mk = 0, int mb = 0) {
     if (!upd) return C;
     const v2f_t E = h ? v2f_t{O.y, er} : v2f_t{O.x, O.y};
     const v2f_t W = h ? v2f_t{O.x, O.y} : v2f_t{wl, O.x};
@@ -369,6 +401,10 @@ __device__ inline v2f_t level2(v2f_t C, v2f_t O, float wl, float er, v2f_t N, v2
     // x0 + 2 = x + 3 column nx - 1)
     if (h == 0) o.x = x0 != 0 ? o.x : C.x;
     if (h == 1) o.y = x0 + 2 != nx - 1 ? o.y : C.y;
+    if constexpr (MSK) {
+        o.x = (mk & (1u << mb)) ? C.x : o.x;
+        o.y = (mk & (4u << mb)) ? C.y : o.y;
+    }
     if (own) {
         chg = fmaxf(chg, fabsf(o.x - C.x));
         chg = fmaxf(chg, fabsf(o.y - C.y));
@@ -421,6 +457,11 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
     const size_t hofs = (size_t)(hon ? yr : 0) * nx + (hon ? hx : 0);
     const int col = side ? 260 : 0;
     constexpr bool ZERO = (F & kFirstZero) != 0;  // level 0 = 0: no phi loads
+    constexpr bool MSK = (F & kMask2d) != 0;
+    // the mask bytes of the lane's chunk (levels 1..K-1 update it; the two
+    // outermost rows are level 0 only)
+    [[maybe_unused]] uint32_t hm = 0;
+    if constexpr (MSK) hm = mask4(a, hon ? (uint32_t)hofs : kOob);
     auto ldh = [&](const float *base, int p) {
         return (hon && p >= 0 && p <= nz - 1) ? ldg4(base + (size_t)p * plane + hofs) : z4;
     };
@@ -501,9 +542,14 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
                         S = lds4(T(l - 1, hr - 1) + col);
                     }
                     float dummy = 0.f;
-                    v = level4<MODE, PRE>(c, side ? inner : 0.f, side ? 0.f : inner, N, S,
-                                          H[l - 1][2], H[l - 1][0], Hr[l - 1], hx, nx,
-                                          hint && !fixedp(p), a, par, false, dummy);
+                    if constexpr (MSK)
+                        v = level4<MODE, PRE, false, true>(c, side ? inner : 0.f, side ? 0.f : inner, N, S,
+                                                           H[l - 1][2], H[l - 1][0], Hr[l - 1], hx, nx,
+                                                           hint && !fixedp(p), a, par, false, dummy, hm);
+                    else
+                        v = level4<MODE, PRE>(c, side ? inner : 0.f, side ? 0.f : inner, N, S,
+                                              H[l - 1][2], H[l - 1][0], Hr[l - 1], hx, nx,
+                                              hint && !fixedp(p), a, par, false, dummy);
                 }
                 H[l][0] = H[l][1];
                 H[l][1] = H[l][2];
@@ -615,7 +661,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
 
     static_assert(!PT || DMA, "pair tiles: LDS-DMA path");
     static_assert(MODE == kJacobi || !PRE, "GS: raw div");
-    static_assert(F == 0 || (MODE == kJacobi && !PRE && DMA), "first pass: Jacobi, raw div, DMA path");
+    static_assert((F & (kFirstRhs | kFirstZero)) == 0 || (MODE == kJacobi && !PRE && DMA),
+                  "first pass: Jacobi, raw div, DMA path");
+    constexpr bool MSK = (F & kMask2d) != 0;
+    static_assert(!MSK || (MODE == kRbgs && DMA), "2-D mask: red-black GS, LDS-DMA path");
     constexpr bool ZERO = (F & kFirstZero) != 0, RHSW = (F & kFirstRhs) != 0;
     constexpr bool PREL = PRE || RHSW;  // the row waves' queues hold the rhs
     // the rhs from raw div (RHSW), the same bits as k_rhs_f32
@@ -747,6 +796,16 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 const uint32_t o = (uint32_t)(((size_t)(rowin ? y : 0) * nx + (xin ? x : 0)) * sizeof(float));
                 bo[j] = xin && rowin ? o : kOob;
                 so[j] = orow[j] ? o : kOob;
+            }
+            // MSK: bit 4 j + k = cell x + k of row j is solid (0 outside the grid)
+            [[maybe_unused]] uint32_t mk = 0;
+            if constexpr (MSK) {
+#pragma unroll
+                for (int j = 0; j < RPW; ++j) {
+                    const uint32_t m4 = mask4(a, bo[j] == kOob ? kOob : bo[j] >> 2);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) mk |= (m4 >> (8 * k)) & 0xffu ? 1u << (4 * j + k) : 0u;
+                }
             }
             // V[j][i]: level 0 of plane z-1+i; Q[j][l][i]: level l of plane
             // (z-l)-1+i after level l is computed; Rq[j][i]: rhs of plane z-i
@@ -917,6 +976,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 // is BP ^ E ^ (j * NWR) mod 2 (BP: see march)
                 constexpr int BPv = decltype(bpc)::value;
                 trace_mark(a.trace, wv, z - zs, 0);
+                // MSK: the mask word made opaque per step, so the lane masks of
+                // its tests (one per row and cell of the step's colour, shared
+                // by the levels) live in SGPRs for one step; hoisted out of the
+                // march they are 8 SGPR pairs across it
+                if constexpr (MSK && CFD_TBR_MSTEP) asm volatile("" : "+v"(mk));
                 float *const pw = E ? st_p1 : st_p0;
                 float *const rw = E ? st_r1 : st_r0;
                 const float *const pr = E ? st_p0 : st_p1;
@@ -1200,9 +1264,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                             const float wl = dpp_from_lower_old(in.wl, Op.y), er = dpp_from_upper_old(in.er, Op.x);
                             // every lane computes (one beyond nx reads zeros and is
                             // never stored: its LDS writes and HBM store are masked)
-                            const v2f_t v = level2(Cp, Op, wl, er, in.N, in.S, Up, Dp,
-                                                   pick2(Rq[j][ROTR ? slk(R - l + 1, K) : l - 1], h), h, x, nx,
-                                                   irow[j] && !fx, gk, orow[j] && p >= z0 && p < z1, chgl[slot(l)]);
+                            const v2f_t v = level2<MSK>(Cp, Op, wl, er, in.N, in.S, Up, Dp,
+                                                        pick2(Rq[j][ROTR ? slk(R - l + 1, K) : l - 1], h), h, x, nx,
+                                                        irow[j] && !fx, gk, orow[j] && p >= z0 && p < z1,
+                                                        chgl[slot(l)], mk, 4 * j + h);
                             if (l < K) {
                                 if constexpr (ROT) {
                                     Q[j][l][sl3(R - l + 1)] = v;
@@ -1497,6 +1562,7 @@ namespace {
 struct TbrShape {
     int K, nwr, rpw;
     bool autopick;  // candidate for rows == 0
+    bool masked = false;  // has a red-black GS instantiation with the 2-D mask (kMask2d)
     int rows() const { return nwr * rpw + 2 - 2 * K; }
 };
 // K = 4: (4, 11, 2) -- 16 output rows, one round of 256 workgroups at 1024^2 --
@@ -1509,9 +1575,14 @@ struct TbrShape {
 // (2, 10, 2): 18-row, 228 workgroups, for the 240 CUs of a partitioned slab.
 // K = 3 shapes also serve the red-black GS (three half-sweeps, 1.5 iterations,
 // per pass: the r02 default); K = 1 only its rollback of one half-sweep.
+// With the 2-D mask one 16-row shape for 4, 2 and 1 levels: a masked launch
+// picks among those only (a masked solve's passes, its shorter last pass and
+// its rollbacks).  (3, 10, 2) with the mask spills 17 VGPRs -- the unmasked
+// one sits at the cap of 168 -- so a masked solve at 3 levels takes the
+// in-place colour passes.
 constexpr TbrShape kShapes[] = {{3, 11, 2, true}, {3, 10, 2, true}, {3, 7, 3, false},
-                                {4, 7, 3, false}, {4, 11, 2, true}, {4, 10, 2, false}, {2, 11, 2, true},
-                                {2, 10, 2, true}, {2, 10, 3, false}, {2, 9, 2, true}, {1, 9, 2, true}};
+                                {4, 7, 3, false}, {4, 11, 2, true, true}, {4, 10, 2, false}, {2, 11, 2, true},
+                                {2, 10, 2, true}, {2, 10, 3, false}, {2, 9, 2, true, true}, {1, 9, 2, true, true}};
 
 int num_cus() {
     static int n = 0;
@@ -1529,6 +1600,15 @@ thread_local int g_last_shape[4] = {0, 0, 0, 0};  // K, row waves, rows per wave
 
 int tbr_cus() { return num_cus() - g_cu_reserve; }
 void set_cu_reserve(int n) { g_cu_reserve = n; }
+
+// Whether a red-black GS pass of `levels` half-sweeps on tiles of `rows` output
+// rows (0: auto) has an instantiation with the 2-D mask.
+bool rbgs3d_tbr_mask_ok(int levels, int rows) {
+    if (jacobi3d_tb_prefetch() != 1) return false;
+    for (const TbrShape &sh : kShapes)
+        if (sh.K == levels && sh.masked && (rows == 0 || sh.rows() == rows)) return true;
+    return false;
+}
 
 // rows = output rows per tile (0: pick the shape and z-chunk by a cost model).
 // One workgroup fills a CU (LDS / VGPRs), so workgroups run in rounds of
@@ -1553,11 +1633,12 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
     const int L = a.ze - a.zb;
     const int nseg = ceil_div(a.nx, 256);
     const int ncu = tbr_cus();
+    const bool masked = MODE == kRbgs && a.mask2d;  // (Jacobi: the slot is rhs_out)
     const TbrShape *best = nullptr;
     int best_zlen = 0;
     double best_cost = 0.0;
     for (const TbrShape &sh : kShapes) {
-        if (sh.K != K || (rows ? sh.rows() != rows : !sh.autopick)) continue;
+        if (sh.K != K || (rows ? sh.rows() != rows : !sh.autopick) || (masked && !sh.masked)) continue;
         const int W = sh.rows(), NR = W + 2 * K;
         const long tiles = (long)nseg * ceil_div(a.ny - 2, W);
         for (int nzc = 1; nzc <= 64; ++nzc) {
@@ -1574,8 +1655,9 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
             if (zchunk > 0) break;
         }
     }
-    if (!best) {
-        set_error("jacobi3d_tbr: no tile shape with %d rows for %d levels per pass", rows, K);
+    if (!best || (masked && pd != 1)) {
+        set_error("jacobi3d_tbr: no %stile shape with %d rows for %d levels per pass", masked ? "masked " : "",
+                  rows, K);
         return CFD_E_INVALID;
     }
     a.nseg = nseg;
@@ -1665,6 +1747,21 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
         CFD_TBR(KV, NW, RP);                                                                 \
     } while (0)
     const int code = best->K * 100 + best->nwr * 10 + best->rpw;
+    if constexpr (MODE == kRbgs) {
+        if (masked) {  // the kShapes entries with `masked`, LDS-DMA path
+#define CFD_TBR_M(KV, NW, RP)                                                                             \
+    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kMask2d>), dim3(blocks), dim3((NW + 1) * 64), 0, \
+                       s, a)
+            switch (code) {
+                case 4 * 100 + 11 * 10 + 2: CFD_TBR_M(4, 11, 2); break;
+                case 2 * 100 + 9 * 10 + 2: CFD_TBR_M(2, 9, 2); break;
+                default: CFD_TBR_M(1, 9, 2); break;
+            }
+#undef CFD_TBR_M
+            CFD_LAUNCH_CHECK();
+            return CFD_OK;
+        }
+    }
     // only the CFD_TBRF shapes below have first-pass instantiations; a first
     // pass on any other shape would silently run as a plain pass (rhs_out
     // never written, phi read from `out`)
@@ -1730,10 +1827,12 @@ int jacobi3d_tbr_first_pass(int K, float *out, const float *div, float *rhs_out,
 // inside a pass of a solve of P half-sweeps per pass and nhalf in all (in =
 // phi, out = phi_tmp as passed to the solve; the kernel reads the count in
 // ws->flags[1], see rbgs_count, and picks h0 and the direction itself).
+// mask2d != NULL: the (ny, nx) solid mask of every plane (kMask2d), on the
+// shapes rbgs3d_tbr_mask_ok accepts; others are an error, so callers ask first.
 int rbgs3d_tbr_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
                     int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
                     int levels, RbgsWs *ws, int rollback, int nhalf, int rows, hipStream_t s,
-                    int lag) {
+                    int lag, const uint8_t *mask2d) {
     if (ze <= zb || ny < 3) return CFD_OK;
     TbrArgs a{};
     a.in = in; a.out = out; a.div = div;
@@ -1746,6 +1845,7 @@ int rbgs3d_tbr_pass(const float *in, float *out, const float *div, int nz, int n
     a.nhalf = nhalf;
     a.count = &ws->flags[1];
     a.lag = lag;
+    a.mask2d = mask2d;
     return tbr_launch<kRbgs>(a, levels, rows, jacobi3d_tb_zchunk(), false, s);
 }
 

@@ -403,8 +403,8 @@ int launch_rhs_f32(const float *div, float *rhs, size_t n, float h2, float dt, h
 template <int C>
 __global__ __launch_bounds__(256) void rbgs3d_color(float *__restrict__ phi,
                                                     const float *__restrict__ div,
-                                                    const uint8_t *__restrict__ mask, int ny,
-                                                    int nx, int z0, int zoff, float cx, float cy,
+                                                    const uint8_t *__restrict__ mask, size_t mask_plane,
+                                                    int ny, int nx, int z0, int zoff, float cx, float cy,
                                                     float cz, float cd, float dt_inv, float tol,
                                                     RbgsWs *ws, int it) {
     if (it > 0 && ws->maxc[it - 1] < tol) {
@@ -420,7 +420,8 @@ __global__ __launch_bounds__(256) void rbgs3d_color(float *__restrict__ phi,
     if (x < nx - 1 && x >= 1 && ((zoff + z + i + x + 1 + C) & 1) == 0) {
         const size_t plane = (size_t)ny * nx;
         const size_t c = (size_t)z * plane + (size_t)i * nx + x;
-        if (!(mask && mask[c])) {
+        // (mask_plane: ny * nx, or 0 for a 2-D mask that serves every plane)
+        if (!(mask && mask[(size_t)z * mask_plane + (size_t)i * nx + x])) {
             const float rhs = -div[c] * dt_inv;
             const float a = cx * (phi[c + 1] + phi[c - 1]);
             const float b = cy * (phi[c + nx] + phi[c - nx]);
@@ -436,14 +437,15 @@ __global__ __launch_bounds__(256) void rbgs3d_color(float *__restrict__ phi,
 
 int rbgs3d_colour_pass(int colour, float *phi, const float *div, const uint8_t *mask, int ny,
                        int nx, int z0, int z1, int zoff, const RbgsConsts &k, RbgsWs *ws, int it,
-                       hipStream_t s) {
+                       hipStream_t s, bool mask2d) {
     if (z1 <= z0 || ny < 3 || nx < 3) return CFD_OK;
     dim3 grid(ceil_div(nx, 256), ny - 2, z1 - z0);
+    const size_t mp = mask2d ? 0 : (size_t)ny * nx;
     if (colour == 0)
-        hipLaunchKernelGGL(rbgs3d_color<0>, grid, dim3(256), 0, s, phi, div, mask, ny, nx, z0, zoff,
+        hipLaunchKernelGGL(rbgs3d_color<0>, grid, dim3(256), 0, s, phi, div, mask, mp, ny, nx, z0, zoff,
                            k.cx, k.cy, k.cz, k.cd, k.dt_inv, k.tol, ws, it);
     else
-        hipLaunchKernelGGL(rbgs3d_color<1>, grid, dim3(256), 0, s, phi, div, mask, ny, nx, z0, zoff,
+        hipLaunchKernelGGL(rbgs3d_color<1>, grid, dim3(256), 0, s, phi, div, mask, mp, ny, nx, z0, zoff,
                            k.cx, k.cy, k.cz, k.cd, k.dt_inv, k.tol, ws, it);
     CFD_LAUNCH_CHECK();
     return CFD_OK;
@@ -486,18 +488,24 @@ int rbgs3d_fused_pass(const float *in, float *out, const float *div, int nz, int
                             2 * iters, ws, s, lag);
 }
 
-// A fused GS pass of `levels` half-sweeps from half-sweep h0, on the tile rows
-// set for that depth (2: 16, 18, 20, 28; 3: 16, 18; 4: 15, 16), else auto.
-int rbgs3d_half_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
-                     int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
-                     int levels, RbgsWs *ws, hipStream_t s, int lag) {
+// The tile rows set for a GS pass of `levels` half-sweeps (2: 16, 18, 20, 28;
+// 3: 16, 18; 4: 15, 16), else 0 = auto.
+static int rbgs3d_half_rows(int levels) {
     const int r = tuning().tb_rows;
     const bool shape_ok = levels == 2   ? (r == 16 || r == 18 || r == 20 || r == 28)
                           : levels == 3 ? (r == 16 || r == 18)
                           : levels == 4 ? (r == 15 || r == 16)
                                         : false;
+    return shape_ok ? r : 0;
+}
+
+// A fused GS pass of `levels` half-sweeps from half-sweep h0, on the tile rows
+// set for that depth, else auto; mask2d: the optional z-invariant solid mask.
+int rbgs3d_half_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
+                     int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
+                     int levels, RbgsWs *ws, hipStream_t s, int lag, const uint8_t *mask2d) {
     return rbgs3d_tbr_pass(in, out, div, nz, ny, nx, zb, ze, fixed_lo, fixed_hi, zoff, k, h0, levels,
-                           ws, 0, 0, shape_ok ? r : 0, s, lag);
+                           ws, 0, 0, rbgs3d_half_rows(levels), s, lag, mask2d);
 }
 
 // One pass of k Jacobi sweeps over planes [zb, ze) (k = 1..4): the single
@@ -696,9 +704,12 @@ int cfd_jacobi3d_zero_f32(const float *div, float *phi, float *phi_tmp, float *r
                             stream);
 }
 
-int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, int ny, int nx,
-                   double dx, double dy, double dz, float dt, int iterations, double tolerance,
-                   float *phi_tmp, void *ws, int *iters_done, void *stream) {
+// cfd_rbgs3d_f32 (mask (nz, ny, nx)) and cfd_rbgs3d_mask2d_f32 (mask2d: mask
+// (ny, nx), every plane's).  Only the 2-D mask fuses: the tall-tile passes
+// hold its bits in registers for the whole z-march (jacobi3d_tbr.hip).
+static int rbgs3d_solve(float *phi, const float *div, const uint8_t *mask, bool mask2d, int nz, int ny, int nx,
+                        double dx, double dy, double dz, float dt, int iterations, double tolerance,
+                        float *phi_tmp, void *ws, int *iters_done, void *stream) {
     CFD_REQUIRE(phi && div && ws, "rbgs3d: null pointer");
     CFD_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1 && iterations >= 0, "rbgs3d: bad arguments");
     hipStream_t s = as_stream(stream);
@@ -709,17 +720,24 @@ int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, in
     if (nz < 3 || ny < 3 || nx < 3 || iterations == 0) return CFD_OK;
     const size_t n = (size_t)nz * ny * nx;
     const int tk = timing_begin(s);
-    if (rbgs3d_fused_ok(phi, phi_tmp, div, mask, nx)) {
+    // the 2-D mask fuses when every launch of the solve -- its passes of P
+    // half-sweeps, a shorter last one, the rollbacks (auto tiles) -- has a
+    // masked instantiation; else the colour passes, the same bits
+    const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
+    const uint8_t *m2 = mask2d ? mask : nullptr;
+    const bool m2_ok = !m2 || ((reinterpret_cast<uintptr_t>(m2) & 3u) == 0 &&
+                               rbgs3d_tbr_mask_ok(P, rbgs3d_half_rows(P)) &&
+                               (H % P == 0 || rbgs3d_tbr_mask_ok(H % P, rbgs3d_half_rows(H % P))));
+    if (m2_ok && rbgs3d_fused_ok(phi, phi_tmp, div, mask2d ? nullptr : mask, nx)) {
         // fused: out-of-place passes of pp iterations (both colours each),
         // ping-pong; the result's buffer and a stop inside a pair pass are
         // resolved on the device after the loop
         if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, nz, 0, nz - 1, s))) return rc;
         // passes of P half-sweeps (colour levels), the last one shorter
-        const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
         float *a = phi, *b = phi_tmp;
         for (int h = 0; h < H; h += P) {
             const int m = H - h >= P ? P : H - h;
-            if ((rc = rbgs3d_half_pass(a, b, div, nz, ny, nx, 1, nz - 1, 1, 1, 0, k, h, m, w, s, 0)))
+            if ((rc = rbgs3d_half_pass(a, b, div, nz, ny, nx, 1, nz - 1, 1, 1, 0, k, h, m, w, s, 0, m2)))
                 return rc;
             float *t = a; a = b; b = t;
         }
@@ -732,16 +750,30 @@ int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, in
         for (int need = 1; need < hpp && k.tol > 0.f; ++need)
             if (!(hpp % 2 == 0 && need % 2 == 1) &&
                 (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, nz, ny, nx, 1, nz - 1, 1, 1, 0, k, 0, need, w, hpp,
-                                      H, 0, s)))
+                                      H, 0, s, 0, m2)))
                 return rc;
         return launch_rbgs_copy(w, phi, phi_tmp, n, hpp, s);
     }
     for (int it = 0; it < iterations; ++it) {
-        if ((rc = rbgs3d_colour_pass(0, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s))) return rc;
-        if ((rc = rbgs3d_colour_pass(1, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s))) return rc;
+        if ((rc = rbgs3d_colour_pass(0, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s, mask2d))) return rc;
+        if ((rc = rbgs3d_colour_pass(1, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s, mask2d))) return rc;
     }
     timing_end(tk, s, iterations);
     return launch_rbgs_finish(w, phi, nullptr, n, iters_done, s);
+}
+
+int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, int ny, int nx,
+                   double dx, double dy, double dz, float dt, int iterations, double tolerance,
+                   float *phi_tmp, void *ws, int *iters_done, void *stream) {
+    return rbgs3d_solve(phi, div, mask, false, nz, ny, nx, dx, dy, dz, dt, iterations, tolerance, phi_tmp, ws,
+                        iters_done, stream);
+}
+
+int cfd_rbgs3d_mask2d_f32(float *phi, const float *div, const uint8_t *mask2d, int nz, int ny, int nx,
+                          double dx, double dy, double dz, float dt, int iterations, double tolerance,
+                          float *phi_tmp, void *ws, int *iters_done, void *stream) {
+    return rbgs3d_solve(phi, div, mask2d, true, nz, ny, nx, dx, dy, dz, dt, iterations, tolerance, phi_tmp, ws,
+                        iters_done, stream);
 }
 
 int cfd_rbgs3d_pass_f32(const float *in, float *out, const float *div, int nz, int ny, int nx,

@@ -275,16 +275,21 @@ def solve_pressure_jacobi3d_zero(phi, div, h, dt, iterations, phi_tmp=None, rhs_
 def solve_pressure_gauss_seidel3d(phi, div, dx, dy, dz, dt, mask, iterations, tolerance,
                                   workspace=None, iters_done=None, phi_tmp=None):
     """3-D red-black generalisation of v5.py:202-226, in place on ``phi``
-    (``phi_tmp``: as in solve_pressure_gauss_seidel_fast)."""
+    (``phi_tmp``: as in solve_pressure_gauss_seidel_fast).  ``mask``: None, an
+    (nz, ny, nx) solid mask (in-place colour passes), or an (ny, nx) mask that
+    applies to every plane (cfd_rbgs3d_mask2d_f32: fused passes, the same bits
+    as the expanded mask)."""
     nz, ny, nx = (int(s) for s in phi.shape)
-    m = _mask_u8(mask, phi.shape)
+    mask2d = mask is not None and mask.dim() == 2
+    m = _mask_u8(mask, (ny, nx) if mask2d else phi.shape)
     need = int(lib().cfd_rbgs_workspace_bytes(int(iterations)))
     ws = workspace
     if ws is None or ws.numel() * ws.element_size() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=phi.device)
     tmp = torch.empty_like(phi) if phi_tmp is None else _like(phi, phi_tmp, "phi_tmp")
     _like(phi, div, "div")
-    call("cfd_rbgs3d_f32", ptr(_f32(phi, "phi")), ptr(_f32(div, "div")), ptr(m), nz, ny, nx, float(dx),
+    call("cfd_rbgs3d_mask2d_f32" if mask2d else "cfd_rbgs3d_f32", ptr(_f32(phi, "phi")), ptr(_f32(div, "div")),
+         ptr(m), nz, ny, nx, float(dx),
          float(dy), float(dz), float(np.float32(dt)), int(iterations), float(tolerance), ptr(_f32(tmp, "phi_tmp")),
          ptr(ws), ptr(iters_done), stream_handle())
     return phi

@@ -759,9 +759,11 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     force_strength = min(1, step / initial_steps), one launch, after the
     predictor and after the projection; ``ibm_mask`` stays the 2-D float64
     array and only its bounding box is visited).  The pressure solve takes the
-    solid mask: phi = zeros, then cfd_rbgs3d_f32 (use_fast_pressure, any
-    spacing) or cfd_jacobi3d_f32 (dx == dy == dz) with ``cylinder_mask``, the
-    2-D mask expanded once to (nz, ny, nx) uint8.  LES as in the cavity
+    solid mask: phi = zeros, then cfd_rbgs3d_mask2d_f32 (use_fast_pressure,
+    any spacing) with ``cylinder_mask2d``, the (ny, nx) uint8 mask that every
+    plane shares -- fused passes whose waves hold its bits in registers -- or
+    cfd_jacobi3d_f32 (dx == dy == dz) with ``cylinder_mask``, the same mask
+    expanded once to (nz, ny, nx), which the vorticity kernel reads too.  LES as in the cavity
     solver.  No host synchronisation per step, except the adaptive dt's one
     read from step 1000 on.
 
@@ -772,10 +774,9 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     |omega| (NaN in the cylinder); with log_diagnostics ``diagnostics`` gains
     ``vorticity_max`` of the step's final unclipped fields.
 
-    Not yet: temporal blocking of the masked 3-D solves (with a mask the
-    Jacobi runs single sweeps and the red-black GS in-place colour passes, so
-    the pressure solve dominates the step: DESIGN.md 4.4), periodic spanwise
-    boundaries, snapshots, float64 and the slab path."""
+    Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
+    single sweeps: DESIGN.md 4.4), masks that vary along z in the fused GS,
+    periodic spanwise boundaries, snapshots, float64 and the slab path."""
 
     def __init__(self, config: CylinderChannel3DConfig):
         super().__init__(config)
@@ -787,8 +788,8 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         self.cylinder_mask_host, self.ibm_mask_host = cyl, ibm
         self.ibm_mask = torch.from_numpy(ibm).to(self.device)
         self.ibm_bbox = host_ibm_bbox(ibm)
-        self.cylinder_mask = (torch.from_numpy(cyl).to(self.device).to(torch.uint8)
-                              .expand(cfg.nz, cfg.ny, cfg.nx).contiguous())
+        self.cylinder_mask2d = torch.from_numpy(cyl).to(self.device).to(torch.uint8).contiguous()
+        self.cylinder_mask = self.cylinder_mask2d.expand(cfg.nz, cfg.ny, cfg.nx).contiguous()
         u, v = host_potential_flow(cfg, self.X, self.Y, self.dist, ibm, np.float32)
         self.u.copy_(torch.from_numpy(u).to(self.device).expand_as(self.u))
         self.v.copy_(torch.from_numpy(v).to(self.device).expand_as(self.v))
@@ -805,8 +806,8 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
                              "use_fast_pressure=True takes any spacing")
         self.phi.zero_()
         if cfg.use_fast_pressure:
-            K.solve_pressure_gauss_seidel3d(self.phi, div_u_star, cfg.dx, cfg.dy, cfg.dz, cfg.dt, self.cylinder_mask,
-                                            cfg.pressure_iterations, cfg.pressure_tolerance, workspace=self._gs_ws,
+            K.solve_pressure_gauss_seidel3d(self.phi, div_u_star, cfg.dx, cfg.dy, cfg.dz, cfg.dt,
+                                            self.cylinder_mask2d, cfg.pressure_iterations, cfg.pressure_tolerance, workspace=self._gs_ws,
                                             iters_done=self._gs_done, phi_tmp=self._phi_tmp)
         else:
             K.solve_pressure_jacobi3d(self.phi, div_u_star, cfg.dx, cfg.dt, self.cylinder_mask,

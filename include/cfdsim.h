@@ -129,7 +129,9 @@ int cfd_jacobi3d_zero_f32(const float *div, float *phi, float *phi_tmp, float *r
  * aligned arrays, blocking not switched off), each iteration runs as ONE fused
  * out-of-place pass over both colours (ping-pong phi/phi_tmp; the result
  * still ends in phi, bit-identical); NULL = in-place colour passes.  3-D:
- * fused only without a mask.  cfd_set_jacobi2d_blocking(1) /
+ * fused without a mask, or with a z-invariant (ny, nx) mask through
+ * cfd_rbgs3d_mask2d_f32; a (nz, ny, nx) mask takes the in-place colour
+ * passes.  cfd_set_jacobi2d_blocking(1) /
  * cfd_set_jacobi3d_blocking(1, ...) switch the fused path off.
  * ws: cfd_rbgs_workspace_bytes(iterations) bytes.
  * iters_done (device int*, optional) receives the iteration count executed. */
@@ -162,10 +164,20 @@ int cfd_rbgs2d_zero_f32_ws(float *phi, const float *div, const uint8_t *mask, in
 /* 3-D red-black generalisation: colour c updates (z+i+j) parity == (1+c)%2.
  * The fused 3-D path runs cfd_get_rbgs3d_levels() half-sweeps per HBM pass
  * (default 4: two iterations; cfd_set_jacobi3d_blocking(2..4, ...) sets it),
- * a stop inside a pass rolled back on the device. */
+ * a stop inside a pass rolled back on the device.  The fused path takes no
+ * mask here: with a (nz, ny, nx) mask the solve runs in-place colour passes.
+ * Only a z-invariant mask fuses, through cfd_rbgs3d_mask2d_f32. */
 int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, int ny, int nx,
                    double dx, double dy, double dz, float dt, int iterations, double tolerance,
                    float *phi_tmp, void *ws, int *iters_done, void *stream);
+/* cfd_rbgs3d_f32 with a z-invariant solid mask: mask2d is uint8 (ny, nx),
+ * nonzero = solid, applied to every plane (NULL = none).  Same bits as
+ * cfd_rbgs3d_f32 with the mask repeated nz times.  Fused (tall tiles, levels
+ * as cfd_get_rbgs3d_levels) under cfd_rbgs3d_f32's conditions plus a 4-byte
+ * aligned mask2d; otherwise in-place colour passes. */
+int cfd_rbgs3d_mask2d_f32(float *phi, const float *div, const uint8_t *mask2d, int nz, int ny, int nx,
+                          double dx, double dy, double dz, float dt, int iterations, double tolerance,
+                          float *phi_tmp, void *ws, int *iters_done, void *stream);
 
 /* ---------------------------------------------------------------- predictor */
 

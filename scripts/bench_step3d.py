@@ -29,8 +29,13 @@ against tests/les3d_reference.py, bit for bit.
 --cylinder: the 3-D cylinder channel leg instead, at the
 default 600 x 180 x 120 grid: cfd_apply_channel_bc_ibm3d_f32 with the mask's
 tight box and with the whole-grid box and cfd_vorticity3d_f32 (ms, algorithmic
-bytes and the fraction of the HBM peak), then CylinderChannel3DSolver.time_step
-with the red-black GS, LES off and on, with the pressure solve's share of it.
+bytes and the fraction of the HBM peak), then the pressure solve alone -- 200
+red-black GS iterations at tolerance 0, alternating window by window: (a)
+cfd_rbgs3d_mask2d_f32 with the 2-D mask at 4 (auto) and at 2 half-sweeps per
+pass, (b) cfd_rbgs3d_f32 with the mask expanded to 3-D (in-place colour
+passes), (c) cfd_rbgs3d_f32 without a mask (the fused kernel's ceiling on this
+grid) -- then CylinderChannel3DSolver.time_step with the red-black GS, LES off
+and on, with the pressure solve's share of it.
 
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
@@ -313,6 +318,53 @@ def bc_ibm_bytes(nz, ny, nx, ibm, bbox):
     return 12 * (rd + wr) + 8 * (i1 - i0) * (j1 - j0)
 
 
+def last_tbr_shape():
+    v = [ctypes.c_int() for _ in range(4)]
+    call("cfd_get_last_tbr_shape", *[ctypes.byref(x) for x in v])
+    return [x.value for x in v]
+
+
+def cylinder_solves(s, rounds, iters=200):
+    """The cylinder channel's pressure solve alone, `iters` iterations at
+    tolerance 0 on the solver's grid and mask: {leg: (mask, blocking levels)}."""
+    c = s.config
+    cells = c.nz * c.ny * c.nx
+    g = torch.Generator(device="cuda").manual_seed(11)
+    div = torch.randn((c.nz, c.ny, c.nx), device="cuda", generator=g) * 1e-3
+    phi, tmp = torch.zeros_like(div), torch.empty_like(div)
+    legs = {"a_mask2d": (s.cylinder_mask2d, 0), "a_mask2d_2_levels": (s.cylinder_mask2d, 2),
+            "b_mask3d": (s.cylinder_mask, 0), "c_unmasked": (None, 0)}
+
+    def run(k):
+        mask, levels = legs[k]
+        call("cfd_set_jacobi3d_blocking", levels, 0, 0)
+        K.solve_pressure_gauss_seidel3d(phi, div, c.dx, c.dy, c.dz, c.dt, mask, iters, 0.0, workspace=s._gs_ws,
+                                        iters_done=s._gs_done, phi_tmp=tmp)
+
+    ms, shapes = {k: [] for k in legs}, {}
+    for k in legs:   # warm up every leg
+        run(k)
+        shapes[k] = last_tbr_shape() if k != "b_mask3d" else None
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k in legs:
+            ms[k].append(window_ms(lambda: run(k), 1))
+    call("cfd_set_jacobi3d_blocking", 0, 0, 0)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    for k, v in ms.items():
+        print(json.dumps({"bench": "cylinder3d_solve", "grid": [c.nz, c.ny, c.nx], "leg": k, "iterations": iters,
+                          "tolerance": 0.0, "last_tbr_shape": shapes[k], "ms": round(med[k], 3),
+                          "ms_min": round(min(v), 3), "ms_max": round(max(v), 3), "rounds": rounds,
+                          "ms_per_iteration": round(med[k] / iters, 4),
+                          "gcell_updates_per_s": round(cells * iters / med[k] / 1e6, 1)}), flush=True)
+    best = min(("a_mask2d", "a_mask2d_2_levels"), key=med.get)
+    print(json.dumps({"bench": "cylinder3d_solve_decision", "fastest_masked": best,
+                      "a_over_b": round(med["a_mask2d"] / med["b_mask3d"], 3),
+                      "a2_over_b": round(med["a_mask2d_2_levels"] / med["b_mask3d"], 3),
+                      "a_over_c": round(med["a_mask2d"] / med["c_unmasked"], 3), "bar": 0.97,
+                      "fused_wins": bool(med[best] < 0.97 * med["b_mask3d"])}), flush=True)
+
+
 def cylinder_leg(rounds, launches, steps):
     """The 3-D cylinder channel at its default 600 x 180 x 120 grid (DESIGN.md
     4.4): the BC + IBM stage with the mask's tight box and with the whole-grid
@@ -355,6 +407,7 @@ def cylinder_leg(rounds, launches, steps):
                           "box_fraction_of_plane": round((i1 - i0) * (j1 - j0) / (ny * nx), 4),
                           "algorithmic_bytes": nbytes, "full_pass_bytes": 24 * cells + 8 * ny * nx,
                           "hbm_fraction": round(nbytes / (med * 1e-3) / HBM_PEAK, 4)}), flush=True)
+    cylinder_solves(s, rounds)
     del s, mag
     torch.cuda.empty_cache()
     ms_solve, n_sweeps = ctypes.c_double(0), ctypes.c_longlong(0)
