@@ -47,6 +47,9 @@ PROTOTYPES = {
                                c_int, c_double, P, P, P, P]),
     "cfd_rbgs3d_mask2d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_float,
                                       c_int, c_double, P, P, P, P]),
+    "cfd_rbgs3d_zper_ghost": (c_int, []),
+    "cfd_rbgs3d_zper_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_float,
+                                    c_int, c_double, P, P, P, P]),
     "cfd_supg_tau2d_f32": (c_int, [P, P, P, c_float, P, c_int, c_int, c_double, c_double, c_float, P]),
     "cfd_convection_supg2d_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_convection_upwind2d_f32": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),
@@ -94,17 +97,28 @@ PROTOTYPES = {
     "cfd_smagorinsky3d_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_double, P]),
     "cfd_predictor3d_les_f32": (c_int, [P, P, P, c_float, c_float, c_double, P, P, P, P, P, c_int, c_int, c_int,
                                         c_double, c_double, c_double, c_float, c_int, P]),
+    "cfd_predictor3d_zper_f32": (c_int, [P, P, P, c_float, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
+                                         c_double, c_float, c_int, P]),
+    "cfd_predictor3d_les_zper_f32": (c_int, [P, P, P, c_float, c_float, c_double, P, P, P, P, P, c_int, c_int,
+                                             c_int, c_double, c_double, c_double, c_float, c_int, P]),
     "cfd_set_predictor3d_config": (c_int, [c_int, c_int, c_int]),
     "cfd_get_last_predictor3d_path": (c_int, [ctypes.POINTER(c_int)]),
     "cfd_divergence3d_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
+    "cfd_divergence3d_zper_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),
     "cfd_project3d_f32": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
                                   c_float, P, P]),
+    "cfd_project3d_zper_f32": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
+                                       c_float, P, P]),
     "cfd_apply_lid_bc3d_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
     "cfd_energy_mean_clip3d_f32": (c_int, [P, P, P, c_size_t, P, c_float, c_float, P]),
     "cfd_apply_channel_bc_ibm3d_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_int,
                                                c_double, c_int, c_int, c_int, c_int, P, P]),
+    "cfd_apply_channel_bc_ibm3d_zper_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_int,
+                                                    c_double, c_int, c_int, c_int, c_int, P, P]),
     "cfd_vorticity3d_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
                                     P]),
+    "cfd_vorticity3d_zper_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
+                                         c_double, P]),
     "cfd_supg_tau2d_f64": (c_int, [P, P, P, c_double, P, c_int, c_int, c_double, c_double, c_double, P]),
     "cfd_convection_supg2d_f64": (c_int, [P, P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_convection_upwind2d_f64": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),

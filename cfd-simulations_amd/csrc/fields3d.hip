@@ -23,6 +23,19 @@ __device__ inline bool interior3(int k, int j, int i, int nz, int ny, int nx) {
     return k >= 1 && k < nz - 1 && j >= 1 && j < ny - 1 && i >= 1 && i < nx - 1;
 }
 
+// ZP (spanwise-periodic z, the *_zper entry points): every plane is interior
+// in z, the U neighbour of plane nz - 1 is plane 0 and the D neighbour of plane
+// 0 is plane nz - 1; the four x / y faces are what they were.  A template
+// parameter of the per-cell kernels: ZP = false is the code it was.
+template <bool ZP>
+__device__ inline bool interior3z(int k, int j, int i, int nz, int ny, int nx) {
+    return (ZP || (k >= 1 && k < nz - 1)) && j >= 1 && j < ny - 1 && i >= 1 && i < nx - 1;
+}
+// the U / D neighbours' indices (CFD_3D_INDEX's names; wrapped when ZP)
+#define CFD_3D_UD(ZP)                                                                 \
+    const size_t cu = (ZP) && k == nz - 1 ? c - (size_t)(nz - 1) * sz : c + sz;       \
+    const size_t cd = (ZP) && k == 0 ? c + (size_t)(nz - 1) * sz : c - sz;
+
 // one thread per cell: blockIdx.y = row, blockIdx.z = plane
 #define CFD_3D_INDEX                                     \
     const int i = blockIdx.x * blockDim.x + threadIdx.x; \
@@ -44,7 +57,7 @@ struct Pred3Nu {
 };
 // M: one Pred3Nu for the array and LES modes, empty for the scalar one (whose
 // argument list, and with it its code, stays what it was before the modes)
-template <bool SUPG, int NM, typename... M>
+template <bool SUPG, int NM, bool ZP, typename... M>
 __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u, const float *__restrict__ v,
                                                      const float *__restrict__ w, float nu,
                                                      float *__restrict__ us, float *__restrict__ vs,
@@ -56,10 +69,11 @@ __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u
     float uo = uc, vo = vc, wo = wc, t = 0.0f;  // the six faces keep f (tau, nu_t: 0)
     [[maybe_unused]] float nt = 0.0f;
     [[maybe_unused]] const Pred3Nu m = {mode...};
-    if (interior3(k, j, i, nz, ny, nx)) {
-        const Nb7 fu = {uc, u[c + 1], u[c - 1], u[c + sy], u[c - sy], u[c + sz], u[c - sz]};
-        const Nb7 fv = {vc, v[c + 1], v[c - 1], v[c + sy], v[c - sy], v[c + sz], v[c - sz]};
-        const Nb7 fw = {wc, w[c + 1], w[c - 1], w[c + sy], w[c - sy], w[c + sz], w[c - sz]};
+    if (interior3z<ZP>(k, j, i, nz, ny, nx)) {
+        CFD_3D_UD(ZP)
+        const Nb7 fu = {uc, u[c + 1], u[c - 1], u[c + sy], u[c - sy], u[cu], u[cd]};
+        const Nb7 fv = {vc, v[c + 1], v[c - 1], v[c + sy], v[c - sy], v[cu], v[cd]};
+        const Nb7 fw = {wc, w[c + 1], w[c - 1], w[c + sy], w[c - sy], w[cu], w[cd]};
         if constexpr (NM == kNu3Array) nu = m.nu_arr[c];
         if constexpr (NM == kNu3Les) {
             nt = smag3_nut(fu, fv, fw, m.c2, kk);
@@ -96,6 +110,7 @@ __global__ __launch_bounds__(256) void k_smagorinsky3d(const float *__restrict__
 }
 
 // ((uE - uW) cx + (vN - vS) cy) + (wU - wD) cz, 0 on the six faces (+ max|div|)
+template <bool ZP>
 __global__ __launch_bounds__(256) void k_divergence3d(const float *__restrict__ u, const float *__restrict__ v,
                                                       const float *__restrict__ w, float *__restrict__ div, int nz,
                                                       int ny, int nx, float cx, float cy, float cz, float *absmax) {
@@ -103,8 +118,10 @@ __global__ __launch_bounds__(256) void k_divergence3d(const float *__restrict__ 
     float m = 0.0f;
     if (cell) {
         float d = 0.0f;
-        if (interior3(k, j, i, nz, ny, nx))
-            d = ((u[c + 1] - u[c - 1]) * cx + (v[c + sy] - v[c - sy]) * cy) + (w[c + sz] - w[c - sz]) * cz;
+        if (interior3z<ZP>(k, j, i, nz, ny, nx)) {
+            CFD_3D_UD(ZP)
+            d = ((u[c + 1] - u[c - 1]) * cx + (v[c + sy] - v[c - sy]) * cy) + (w[cu] - w[cd]) * cz;
+        }
         div[c] = d;
         const float a = fabsf(d);
         if (a > m) m = a;
@@ -114,6 +131,7 @@ __global__ __launch_bounds__(256) void k_divergence3d(const float *__restrict__ 
 
 // gradient of phi (0 on the faces), u = u* - dt gx, v = v* - dt gy,
 // w = w* - dt gz; gradmax <- max sqrt((gx^2 + gy^2) + gz^2)
+template <bool ZP>
 __global__ __launch_bounds__(256) void k_project3d(const float *__restrict__ phi, const float *__restrict__ us,
                                                    const float *__restrict__ vs, const float *__restrict__ ws,
                                                    float *__restrict__ u, float *__restrict__ v,
@@ -123,10 +141,11 @@ __global__ __launch_bounds__(256) void k_project3d(const float *__restrict__ phi
     float m = 0.0f;
     if (cell) {
         float uo = us[c], vo = vs[c], wo = ws[c];  // the faces copy u* through
-        if (interior3(k, j, i, nz, ny, nx)) {
+        if (interior3z<ZP>(k, j, i, nz, ny, nx)) {
+            CFD_3D_UD(ZP)
             const float gx = (phi[c + 1] - phi[c - 1]) * cx;
             const float gy = (phi[c + sy] - phi[c - sy]) * cy;
-            const float gz = (phi[c + sz] - phi[c - sz]) * cz;
+            const float gz = (phi[cu] - phi[cd]) * cz;
             uo = uo - dt * gx;
             vo = vo - dt * gy;
             wo = wo - dt * gz;
@@ -194,6 +213,12 @@ __global__ void k_lid_bc3d(float *__restrict__ u, float *__restrict__ v, float *
 // [i0, i1) x [j0, j1) of the mask clipped to the cells left over.  The mask is
 // read inside the box only (0 elsewhere), so the stage costs its faces plus
 // the box and not a pass over the fields.
+//
+// ZP (cfd_apply_channel_bc_ibm3d_zper_f32, spanwise-periodic): the assignments
+// without the face step.  There are no face planes: every plane's cells
+// (k, i, j <= nx-2) are owners, a cell (k, i, j') belongs to the owner
+// (k, i, min(j', nx-2)), and the visited ranges are the wall rows, the columns
+// 0 and nx-2 and the clipped box on all nz planes.
 struct BcIbm3 {
     float *u, *v, *w;
     const double *y, *m;
@@ -205,6 +230,7 @@ struct BcIbm3 {
     double *force;  // += sum (before - after) of u, v, w over the cells with m > 0
 };
 
+template <bool ZP>
 __device__ inline void bc_ibm3_own(const BcIbm3 &a, int k, int i, int j, double (&f)[3]) {
     const size_t sy = (size_t)a.nx, sz = (size_t)a.ny * a.nx;
     const size_t c = (size_t)k * sz + (size_t)i * sy + j;
@@ -214,7 +240,7 @@ __device__ inline void bc_ibm3_own(const BcIbm3 &a, int k, int i, int j, double 
     const bool wall = i == 0 || i == a.ny - 1, east = j == a.nx - 2;
     const bool keep = !wall && j != 0;  // the assignments leave the owner's own value
     const double mv = mk(j), me = east ? mk(a.nx - 1) : 0.0;
-    if (keep && !east && k != 1 && k != a.nz - 2 && !(mv > 0.0)) return;  // nothing to write
+    if (keep && !east && (ZP || (k != 1 && k != a.nz - 2)) && !(mv > 0.0)) return;  // nothing to write
     float b[3] = {0.0f, 0.0f, 0.0f};
     if (keep) {
         b[0] = a.u[c];
@@ -241,6 +267,7 @@ __device__ inline void bc_ibm3_own(const BcIbm3 &a, int k, int i, int j, double 
     };
     put(c, mv, false, keep);
     if (east) put(c + 1, me, false, false);
+    if constexpr (ZP) return;
     if (k == 1) {
         put(c - sz, mv, true, false);
         if (east) put(c - sz + 1, me, true, false);
@@ -251,39 +278,41 @@ __device__ inline void bc_ibm3_own(const BcIbm3 &a, int k, int i, int j, double 
     }
 }
 
+template <bool ZP>
 __global__ __launch_bounds__(256) void k_channel_bc_ibm3d(BcIbm3 a, size_t n_plane, size_t n_rows, size_t n_cols,
                                                           size_t n_box, int bi0, int bj0, int bh, int bw) {
     __shared__ double part[4][3];
     double f[3] = {0.0, 0.0, 0.0};
     const size_t total = n_plane + n_rows + n_cols + n_box;
     const size_t ex = (size_t)(a.nx - 1);  // owners of a row
+    constexpr int KB = ZP ? 0 : 2;         // first plane of the three ranges after n_plane (ZP: n_plane = 0)
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         size_t r = t;
         if (r < n_plane) {  // planes 1 and nz - 2
             const int i = (int)(r / ex), j = (int)(r % ex);
-            bc_ibm3_own(a, 1, i, j, f);
-            if (a.nz > 3) bc_ibm3_own(a, a.nz - 2, i, j, f);
+            bc_ibm3_own<ZP>(a, 1, i, j, f);
+            if (a.nz > 3) bc_ibm3_own<ZP>(a, a.nz - 2, i, j, f);
             continue;
         }
         r -= n_plane;
         if (r < n_rows) {  // the wall rows of planes 2 .. nz - 3
-            const int k = 2 + (int)(r / (2 * ex));
+            const int k = KB + (int)(r / (2 * ex));
             const size_t q = r % (2 * ex);
-            bc_ibm3_own(a, k, q < ex ? 0 : a.ny - 1, (int)(q % ex), f);
+            bc_ibm3_own<ZP>(a, k, q < ex ? 0 : a.ny - 1, (int)(q % ex), f);
             continue;
         }
         r -= n_rows;
         if (r < n_cols) {  // columns 0 and nx - 2 of rows 1 .. ny - 2 of those planes
             const size_t per = 2 * (size_t)(a.ny - 2);
-            const int k = 2 + (int)(r / per);
+            const int k = KB + (int)(r / per);
             const size_t q = r % per;
-            bc_ibm3_own(a, k, 1 + (int)(q >> 1), (q & 1) ? a.nx - 2 : 0, f);
+            bc_ibm3_own<ZP>(a, k, 1 + (int)(q >> 1), (q & 1) ? a.nx - 2 : 0, f);
             continue;
         }
         r -= n_cols;  // the rest of the mask's box on those planes
         const size_t per = (size_t)bh * bw;
         const size_t q = r % per;
-        bc_ibm3_own(a, 2 + (int)(r / per), bi0 + (int)(q / bw), bj0 + (int)(q % bw), f);
+        bc_ibm3_own<ZP>(a, KB + (int)(r / per), bi0 + (int)(q / bw), bj0 + (int)(q % bw), f);
     }
     if (!a.force) return;
 #pragma unroll
@@ -304,6 +333,7 @@ __global__ __launch_bounds__(256) void k_channel_bc_ibm3d(BcIbm3 a, size_t n_pla
 // divisions by f32(2 d)), 0 on the six faces, NaN where mask != 0; mag =
 // sqrt((ox ox + oy oy) + oz oz); absmax <- nanmax(mag).  Null outputs are
 // not stored.
+template <bool ZP>
 __global__ __launch_bounds__(256) void k_vorticity3d(const float *__restrict__ u, const float *__restrict__ v,
                                                      const float *__restrict__ w, const uint8_t *__restrict__ mask,
                                                      float *__restrict__ ox, float *__restrict__ oy,
@@ -315,9 +345,10 @@ __global__ __launch_bounds__(256) void k_vorticity3d(const float *__restrict__ u
         float x = 0.0f, y = 0.0f, z = 0.0f, g = 0.0f;
         if (mask && mask[c]) {
             x = y = z = g = __builtin_nanf("");
-        } else if (interior3(k, j, i, nz, ny, nx)) {
-            x = (w[c + sy] - w[c - sy]) / dy2 - (v[c + sz] - v[c - sz]) / dz2;
-            y = (u[c + sz] - u[c - sz]) / dz2 - (w[c + 1] - w[c - 1]) / dx2;
+        } else if (interior3z<ZP>(k, j, i, nz, ny, nx)) {
+            CFD_3D_UD(ZP)
+            x = (w[c + sy] - w[c - sy]) / dy2 - (v[cu] - v[cd]) / dz2;
+            y = (u[cu] - u[cd]) / dz2 - (w[c + 1] - w[c - 1]) / dx2;
             z = (v[c + 1] - v[c - 1]) / dx2 - (u[c + sy] - u[c - sy]) / dy2;
             g = sqrtf((x * x + y * y) + z * z);
             if (g > m) m = g;  // a NaN never wins
@@ -431,7 +462,8 @@ extern "C" {
 
 // The three entry points of the fused predictor (nm: the viscosity mode).
 // nu_arr (kNu3Array) is an input, nut (kNu3Les, may be null) an output.
-static int predictor3d_run(const char *who, int nm, const float *u, const float *v, const float *w, float nu,
+static int predictor3d_run(const char *who, int nm, bool zper, const float *u, const float *v, const float *w,
+                           float nu,
                            const float *nu_arr, float art, double cs, float *u_star, float *v_star, float *w_star,
                            float *tau, float *nut, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
                            int use_supg, void *stream) {
@@ -490,7 +522,7 @@ static int predictor3d_run(const char *who, int nm, const float *u, const float 
         a.c2 = c2;
         a.art = art;
         const int rows = tuning().pred3_rows ? tuning().pred3_rows : 2;
-        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, nm, vec, rows, 0, s));
+        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, nm, vec, rows, 0, s, zper));
         g_last_pred3[0] = 1;
         g_last_pred3[1] = vec;
     } else {
@@ -499,15 +531,21 @@ static int predictor3d_run(const char *who, int nm, const float *u, const float 
 #define CFD_PRED3_CELL(KERNEL, ...)                                                                        \
     hipLaunchKernelGGL(KERNEL, g, dim3(256), 0, s, u, v, w, nu, u_star, v_star, w_star, tau, nz, ny, nx, dt, k, \
                        ##__VA_ARGS__)
-        if (nm == kNu3Les) {
-            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, Pred3Nu>), m);
-            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, Pred3Nu>), m);
+        if (zper && nm == kNu3Les) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, true, Pred3Nu>), m);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, true, Pred3Nu>), m);
+        } else if (zper) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar, true>));
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar, true>));
+        } else if (nm == kNu3Les) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, false, Pred3Nu>), m);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, false, Pred3Nu>), m);
         } else if (nm == kNu3Array) {
-            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Array, Pred3Nu>), m);
-            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Array, Pred3Nu>), m);
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Array, false, Pred3Nu>), m);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Array, false, Pred3Nu>), m);
         } else {
-            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar>));
-            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar>));
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar, false>));
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar, false>));
         }
 #undef CFD_PRED3_CELL
         g_last_pred3[0] = 0;
@@ -521,22 +559,37 @@ static int predictor3d_run(const char *who, int nm, const float *u, const float 
 int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
                         float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
                         double dz, float dt, int use_supg, void *stream) {
-    return predictor3d_run("predictor3d", kNu3Scalar, u, v, w, nu_eff, nullptr, 0.0f, 0.0, u_star, v_star, w_star, tau,
-                           nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+    return predictor3d_run("predictor3d", kNu3Scalar, false, u, v, w, nu_eff, nullptr, 0.0f, 0.0, u_star, v_star,
+                           w_star, tau, nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
 }
 
 int cfd_predictor3d_nu_f32(const float *u, const float *v, const float *w, const float *nu_eff, float *u_star,
                            float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
                            double dz, float dt, int use_supg, void *stream) {
-    return predictor3d_run("predictor3d_nu", kNu3Array, u, v, w, 0.0f, nu_eff, 0.0f, 0.0, u_star, v_star, w_star, tau,
-                           nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+    return predictor3d_run("predictor3d_nu", kNu3Array, false, u, v, w, 0.0f, nu_eff, 0.0f, 0.0, u_star, v_star,
+                           w_star, tau, nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
 }
 
 int cfd_predictor3d_les_f32(const float *u, const float *v, const float *w, float nu, float art_visc, double cs,
                             float *u_star, float *v_star, float *w_star, float *tau, float *nu_t, int nz, int ny,
                             int nx, double dx, double dy, double dz, float dt, int use_supg, void *stream) {
-    return predictor3d_run("predictor3d_les", kNu3Les, u, v, w, nu, nullptr, art_visc, cs, u_star, v_star, w_star, tau,
-                           nu_t, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+    return predictor3d_run("predictor3d_les", kNu3Les, false, u, v, w, nu, nullptr, art_visc, cs, u_star, v_star,
+                           w_star, tau, nu_t, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+}
+
+int cfd_predictor3d_zper_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
+                             float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,
+                             double dz, float dt, int use_supg, void *stream) {
+    return predictor3d_run("predictor3d_zper", kNu3Scalar, true, u, v, w, nu_eff, nullptr, 0.0f, 0.0, u_star, v_star,
+                           w_star, tau, nullptr, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
+}
+
+int cfd_predictor3d_les_zper_f32(const float *u, const float *v, const float *w, float nu, float art_visc, double cs,
+                                 float *u_star, float *v_star, float *w_star, float *tau, float *nu_t, int nz,
+                                 int ny, int nx, double dx, double dy, double dz, float dt, int use_supg,
+                                 void *stream) {
+    return predictor3d_run("predictor3d_les_zper", kNu3Les, true, u, v, w, nu, nullptr, art_visc, cs, u_star, v_star,
+                           w_star, tau, nu_t, nz, ny, nx, dx, dy, dz, dt, use_supg, stream);
 }
 
 int cfd_smagorinsky3d_f32(const float *u, const float *v, const float *w, float *nu_t, int nz, int ny, int nx,
@@ -566,13 +619,50 @@ int cfd_get_last_predictor3d_path(int *cells_per_lane) {
     return g_last_pred3[0];
 }
 
+static int divergence3d_run(const char *who, bool zper, const float *u, const float *v, const float *w, float *div,
+                            int nz, int ny, int nx, double dx, double dy, double dz, float *absmax, void *stream) {
+    CFD_REQUIRE(u && v && w && div, "%s: null pointer", who);
+    CFD_REQUIRE(div != u && div != v && div != w, "%s: div must not alias an input", who);
+    CFD_SHAPE3D(who, nz, ny, nx);
+    const float cx = (float)(0.5 / dx), cy = (float)(0.5 / dy), cz = (float)(0.5 / dz);
+    if (zper)
+        hipLaunchKernelGGL(k_divergence3d<true>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, div, nz,
+                           ny, nx, cx, cy, cz, absmax);
+    else
+        hipLaunchKernelGGL(k_divergence3d<false>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, div,
+                           nz, ny, nx, cx, cy, cz, absmax);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
 int cfd_divergence3d_f32(const float *u, const float *v, const float *w, float *div, int nz, int ny, int nx,
                          double dx, double dy, double dz, float *absmax, void *stream) {
-    CFD_REQUIRE(u && v && w && div, "divergence3d: null pointer");
-    CFD_REQUIRE(div != u && div != v && div != w, "divergence3d: div must not alias an input");
-    CFD_SHAPE3D("divergence3d", nz, ny, nx);
-    hipLaunchKernelGGL(k_divergence3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, div, nz, ny, nx,
-                       (float)(0.5 / dx), (float)(0.5 / dy), (float)(0.5 / dz), absmax);
+    return divergence3d_run("divergence3d", false, u, v, w, div, nz, ny, nx, dx, dy, dz, absmax, stream);
+}
+
+int cfd_divergence3d_zper_f32(const float *u, const float *v, const float *w, float *div, int nz, int ny, int nx,
+                              double dx, double dy, double dz, float *absmax, void *stream) {
+    return divergence3d_run("divergence3d_zper", true, u, v, w, div, nz, ny, nx, dx, dy, dz, absmax, stream);
+}
+
+static int project3d_run(const char *who, bool zper, const float *phi, const float *u_star, const float *v_star,
+                         const float *w_star, float *u, float *v, float *w, int nz, int ny, int nx, double dx,
+                         double dy, double dz, float dt, float *gradmax, void *stream) {
+    CFD_REQUIRE(phi && u_star && v_star && w_star && u && v && w, "%s: null pointer", who);
+    const float *in[4] = {phi, u_star, v_star, w_star};
+    float *out[3] = {u, v, w};
+    for (int o = 0; o < 3; ++o) {
+        for (int q = 0; q < 4; ++q) CFD_REQUIRE(out[o] != in[q], "%s: outputs must not alias inputs", who);
+        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "%s: outputs must not alias each other", who);
+    }
+    CFD_SHAPE3D(who, nz, ny, nx);
+    const float cx = (float)(0.5 / dx), cy = (float)(0.5 / dy), cz = (float)(0.5 / dz);
+    if (zper)
+        hipLaunchKernelGGL(k_project3d<true>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), phi, u_star, v_star,
+                           w_star, u, v, w, nz, ny, nx, cx, cy, cz, dt, gradmax);
+    else
+        hipLaunchKernelGGL(k_project3d<false>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), phi, u_star,
+                           v_star, w_star, u, v, w, nz, ny, nx, cx, cy, cz, dt, gradmax);
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }
@@ -580,18 +670,15 @@ int cfd_divergence3d_f32(const float *u, const float *v, const float *w, float *
 int cfd_project3d_f32(const float *phi, const float *u_star, const float *v_star, const float *w_star, float *u,
                       float *v, float *w, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
                       float *gradmax, void *stream) {
-    CFD_REQUIRE(phi && u_star && v_star && w_star && u && v && w, "project3d: null pointer");
-    const float *in[4] = {phi, u_star, v_star, w_star};
-    float *out[3] = {u, v, w};
-    for (int o = 0; o < 3; ++o) {
-        for (int q = 0; q < 4; ++q) CFD_REQUIRE(out[o] != in[q], "project3d: outputs must not alias inputs");
-        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "project3d: outputs must not alias each other");
-    }
-    CFD_SHAPE3D("project3d", nz, ny, nx);
-    hipLaunchKernelGGL(k_project3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), phi, u_star, v_star, w_star,
-                       u, v, w, nz, ny, nx, (float)(0.5 / dx), (float)(0.5 / dy), (float)(0.5 / dz), dt, gradmax);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return project3d_run("project3d", false, phi, u_star, v_star, w_star, u, v, w, nz, ny, nx, dx, dy, dz, dt, gradmax,
+                         stream);
+}
+
+int cfd_project3d_zper_f32(const float *phi, const float *u_star, const float *v_star, const float *w_star, float *u,
+                           float *v, float *w, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                           float *gradmax, void *stream) {
+    return project3d_run("project3d_zper", true, phi, u_star, v_star, w_star, u, v, w, nz, ny, nx, dx, dy, dz, dt,
+                         gradmax, stream);
 }
 
 int cfd_apply_lid_bc3d_f32(float *u, float *v, float *w, int nz, int ny, int nx, float u_lid, void *stream) {
@@ -621,16 +708,18 @@ int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *o
     return CFD_OK;
 }
 
-int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y, const double *ibm_mask2d, int nz,
-                                   int ny, int nx, double y_max, double v_inf, int step, double force_strength,
-                                   int i0, int i1, int j0, int j1, double *force_out, void *stream) {
-    CFD_REQUIRE(u && v && w && y, "apply_channel_bc_ibm3d: null pointer");
-    CFD_REQUIRE(u != v && u != w && v != w, "apply_channel_bc_ibm3d: u, v, w must be three arrays");
-    CFD_SHAPE3D("apply_channel_bc_ibm3d", nz, ny, nx);
+// cfd_apply_channel_bc_ibm3d_f32 and, zper, cfd_apply_channel_bc_ibm3d_zper_f32
+static int channel_bc_ibm3d_run(const char *who, bool zper, float *u, float *v, float *w, const double *y,
+                                const double *ibm_mask2d, int nz, int ny, int nx, double y_max, double v_inf,
+                                int step, double force_strength, int i0, int i1, int j0, int j1, double *force_out,
+                                void *stream) {
+    CFD_REQUIRE(u && v && w && y, "%s: null pointer", who);
+    CFD_REQUIRE(u != v && u != w && v != w, "%s: u, v, w must be three arrays", who);
+    CFD_SHAPE3D(who, nz, ny, nx);
     CFD_REQUIRE(i0 >= 0 && i0 <= i1 && i1 <= ny && j0 >= 0 && j0 <= j1 && j1 <= nx,
-                "apply_channel_bc_ibm3d: box [%d, %d) x [%d, %d) outside the (%d, %d) plane", i0, i1, j0, j1, ny, nx);
-    CFD_REQUIRE(!ibm_mask2d || (i0 < i1 && j0 < j1), "apply_channel_bc_ibm3d: empty box [%d, %d) x [%d, %d) with a mask",
-                i0, i1, j0, j1);
+                "%s: box [%d, %d) x [%d, %d) outside the (%d, %d) plane", who, i0, i1, j0, j1, ny, nx);
+    CFD_REQUIRE(!ibm_mask2d || (i0 < i1 && j0 < j1), "%s: empty box [%d, %d) x [%d, %d) with a mask", who, i0, i1,
+                j0, j1);
     BcIbm3 a;
     a.u = u;
     a.v = v;
@@ -649,17 +738,59 @@ int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y
     a.j0 = j0;
     a.j1 = j1;
     a.force = force_out;
-    // the four ranges of owners (k_channel_bc_ibm3d)
-    const size_t mid = nz > 4 ? (size_t)(nz - 4) : 0, ex = (size_t)(nx - 1);
+    // the four ranges of owners (k_channel_bc_ibm3d); periodic: no face planes, the other three on all planes
+    const size_t mid = zper ? (size_t)nz : (nz > 4 ? (size_t)(nz - 4) : 0), ex = (size_t)(nx - 1);
     const int bi0 = i0 > 1 ? i0 : 1, bi1 = i1 < ny - 1 ? i1 : ny - 1;
     const int bj0 = j0 > 1 ? j0 : 1, bj1 = j1 < nx - 2 ? j1 : nx - 2;
     const int bh = bi1 > bi0 ? bi1 - bi0 : 0, bw = bj1 > bj0 ? bj1 - bj0 : 0;
-    const size_t n_plane = (size_t)ny * ex, n_rows = mid * 2 * ex, n_cols = mid * 2 * (size_t)(ny - 2);
+    const size_t n_plane = zper ? 0 : (size_t)ny * ex, n_rows = mid * 2 * ex, n_cols = mid * 2 * (size_t)(ny - 2);
     const size_t n_box = ibm_mask2d ? mid * (size_t)bh * bw : 0;
     size_t blocks = (n_plane + n_rows + n_cols + n_box + 255) / 256;
     if (blocks > ((size_t)1 << 20)) blocks = (size_t)1 << 20;  // the kernel strides
-    hipLaunchKernelGGL(k_channel_bc_ibm3d, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a, n_plane, n_rows,
-                       n_cols, n_box, bi0, bj0, bh, bw);
+    if (zper)
+        hipLaunchKernelGGL(k_channel_bc_ibm3d<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a,
+                           n_plane, n_rows, n_cols, n_box, bi0, bj0, bh, bw);
+    else
+        hipLaunchKernelGGL(k_channel_bc_ibm3d<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), a,
+                           n_plane, n_rows, n_cols, n_box, bi0, bj0, bh, bw);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
+int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y, const double *ibm_mask2d, int nz,
+                                   int ny, int nx, double y_max, double v_inf, int step, double force_strength,
+                                   int i0, int i1, int j0, int j1, double *force_out, void *stream) {
+    return channel_bc_ibm3d_run("apply_channel_bc_ibm3d", false, u, v, w, y, ibm_mask2d, nz, ny, nx, y_max, v_inf,
+                                step, force_strength, i0, i1, j0, j1, force_out, stream);
+}
+
+int cfd_apply_channel_bc_ibm3d_zper_f32(float *u, float *v, float *w, const double *y, const double *ibm_mask2d,
+                                        int nz, int ny, int nx, double y_max, double v_inf, int step,
+                                        double force_strength, int i0, int i1, int j0, int j1, double *force_out,
+                                        void *stream) {
+    return channel_bc_ibm3d_run("apply_channel_bc_ibm3d_zper", true, u, v, w, y, ibm_mask2d, nz, ny, nx, y_max,
+                                v_inf, step, force_strength, i0, i1, j0, j1, force_out, stream);
+}
+
+static int vorticity3d_run(const char *who, bool zper, const float *u, const float *v, const float *w,
+                           const uint8_t *mask, float *ox, float *oy, float *oz, float *mag, float *absmax, int nz,
+                           int ny, int nx, double dx, double dy, double dz, void *stream) {
+    CFD_REQUIRE(u && v && w, "%s: null pointer", who);
+    CFD_REQUIRE(ox || oy || oz || mag || absmax, "%s: no output given", who);
+    float *out[4] = {ox, oy, oz, mag};
+    for (int o = 0; o < 4; ++o) {
+        if (!out[o]) continue;
+        CFD_REQUIRE(out[o] != u && out[o] != v && out[o] != w, "%s: outputs must not alias inputs", who);
+        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "%s: outputs must not alias each other", who);
+    }
+    CFD_SHAPE3D(who, nz, ny, nx);
+    const float dx2 = (float)(2.0 * dx), dy2 = (float)(2.0 * dy), dz2 = (float)(2.0 * dz);
+    if (zper)
+        hipLaunchKernelGGL(k_vorticity3d<true>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, mask, ox,
+                           oy, oz, mag, absmax, nz, ny, nx, dx2, dy2, dz2);
+    else
+        hipLaunchKernelGGL(k_vorticity3d<false>, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, mask, ox,
+                           oy, oz, mag, absmax, nz, ny, nx, dx2, dy2, dz2);
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }
@@ -667,19 +798,15 @@ int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y
 int cfd_vorticity3d_f32(const float *u, const float *v, const float *w, const uint8_t *mask, float *ox, float *oy,
                         float *oz, float *mag, float *absmax, int nz, int ny, int nx, double dx, double dy, double dz,
                         void *stream) {
-    CFD_REQUIRE(u && v && w, "vorticity3d: null pointer");
-    CFD_REQUIRE(ox || oy || oz || mag || absmax, "vorticity3d: no output given");
-    float *out[4] = {ox, oy, oz, mag};
-    for (int o = 0; o < 4; ++o) {
-        if (!out[o]) continue;
-        CFD_REQUIRE(out[o] != u && out[o] != v && out[o] != w, "vorticity3d: outputs must not alias inputs");
-        for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "vorticity3d: outputs must not alias each other");
-    }
-    CFD_SHAPE3D("vorticity3d", nz, ny, nx);
-    hipLaunchKernelGGL(k_vorticity3d, grid3d(nz, ny, nx), dim3(256), 0, as_stream(stream), u, v, w, mask, ox, oy, oz,
-                       mag, absmax, nz, ny, nx, (float)(2.0 * dx), (float)(2.0 * dy), (float)(2.0 * dz));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return vorticity3d_run("vorticity3d", false, u, v, w, mask, ox, oy, oz, mag, absmax, nz, ny, nx, dx, dy, dz,
+                           stream);
+}
+
+int cfd_vorticity3d_zper_f32(const float *u, const float *v, const float *w, const uint8_t *mask, float *ox,
+                             float *oy, float *oz, float *mag, float *absmax, int nz, int ny, int nx, double dx,
+                             double dy, double dz, void *stream) {
+    return vorticity3d_run("vorticity3d_zper", true, u, v, w, mask, ox, oy, oz, mag, absmax, nz, ny, nx, dx, dy, dz,
+                           stream);
 }
 
 }  // extern "C"

@@ -574,6 +574,44 @@ static int jacobi3d_blocked_solve(const float *div, float *phi, float *phi_tmp, 
     return CFD_OK;
 }
 
+// ------------------------------------------------- periodic z (cfd_rbgs3d_zper_f32)
+// Ghost planes of a z-periodic array of (nz + 2 G, ny, nx), owned planes
+// G .. G + nz - 1: the g planes after the owned range take the first g owned
+// planes, [G, G + g) -> [G + nz, G + nz + g), and the g planes before it the
+// last g, [G + nz - g, G + nz) -> [G - g, G).  One launch for both ends, one
+// element of V (float4 where a plane is a whole number of them, else float)
+// per lane and step, streaming stores: the ghosts are next read by another
+// launch.  Sources and destinations never overlap (nz >= g).
+constexpr int kZperGhost = 4;
+typedef float zper_f4 __attribute__((ext_vector_type(4)));
+
+template <typename V>
+__global__ __launch_bounds__(256) void k_zper_wrap(V *p, size_t pv, int nz, int G, int g) {
+    const size_t half = (size_t)g * pv;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < 2 * half; t += (size_t)gridDim.x * blockDim.x) {
+        const bool hi = t < half;  // the planes after the owned range
+        const size_t r = hi ? t : t - half;
+        const size_t src = (size_t)(hi ? G : G + nz - g) * pv + r;
+        const size_t dst = (size_t)(hi ? G + nz : G - g) * pv + r;
+        __builtin_nontemporal_store(p[src], p + dst);
+    }
+}
+
+static int launch_zper_wrap(float *p, int nz, int ny, int nx, int G, int g, hipStream_t s) {
+    const size_t plane = (size_t)ny * nx;
+    const bool v4 = plane % 4 == 0 && aligned16(p);
+    const size_t pv = v4 ? plane / 4 : plane;
+    size_t blocks = (2 * (size_t)g * pv + 255) / 256;
+    if (blocks > 16384) blocks = 16384;  // the kernel strides
+    if (v4)
+        hipLaunchKernelGGL(k_zper_wrap<zper_f4>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           reinterpret_cast<zper_f4 *>(p), pv, nz, G, g);
+    else
+        hipLaunchKernelGGL(k_zper_wrap<float>, dim3((unsigned)blocks), dim3(256), 0, s, p, pv, nz, G, g);
+    CFD_LAUNCH_CHECK();
+    return CFD_OK;
+}
+
 }  // namespace cfd
 
 using namespace cfd;
@@ -774,6 +812,73 @@ int cfd_rbgs3d_mask2d_f32(float *phi, const float *div, const uint8_t *mask2d, i
                           float *phi_tmp, void *ws, int *iters_done, void *stream) {
     return rbgs3d_solve(phi, div, mask2d, true, nz, ny, nx, dx, dy, dz, dt, iterations, tolerance, phi_tmp, ws,
                         iters_done, stream);
+}
+
+int cfd_rbgs3d_zper_ghost(void) { return kZperGhost; }
+
+// cfd_rbgs3d_mask2d_f32 with a periodic z: rbgs3d_solve's two routes on the
+// slab layout (owned planes G .. G + nz - 1 of nz + 2 G, both ends non-fixed,
+// so the fused passes recompute the inner ghost planes' intermediate colours
+// as in cfd_slab_rbgs3d_f32) with the ghost planes wrapped after every pass
+// (fused: G deep) or colour (in place: one plane).
+int cfd_rbgs3d_zper_f32(float *phi, float *div, const uint8_t *mask2d, int nz, int ny, int nx, double dx,
+                        double dy, double dz, float dt, int iterations, double tolerance, float *phi_tmp, void *ws,
+                        int *iters_done, void *stream) {
+    CFD_REQUIRE(phi && div && ws, "rbgs3d_zper: null pointer");
+    CFD_REQUIRE(ny >= 1 && nx >= 1 && iterations >= 0, "rbgs3d_zper: bad arguments");
+    CFD_REQUIRE(nz >= 4 && nz % 2 == 0,
+                "rbgs3d_zper: nz = %d: a periodic z needs an even nz >= 4 (the two planes of a wrap must have "
+                "opposite colour parity)", nz);
+    CFD_REQUIRE(phi != phi_tmp && phi != div && phi_tmp != div,
+                "rbgs3d_zper: phi, phi_tmp and div must be three arrays");
+    hipStream_t s = as_stream(stream);
+    const RbgsConsts k = rbgs3d_consts(dx, dy, dz, dt, tolerance);
+    RbgsWs *w = reinterpret_cast<RbgsWs *>(ws);
+    int rc = launch_rbgs_init(w, iterations, k.tol, iters_done, s);
+    if (rc) return rc;
+    if (ny < 3 || nx < 3 || iterations == 0) return CFD_OK;
+    constexpr int G = kZperGhost;
+    const int nzt = nz + 2 * G, zb = G, ze = G + nz;
+    const int zoff = 0;  // the parity of -G: local plane G is global plane 0
+    const size_t n = (size_t)nzt * ny * nx;
+    // the ghosts of the initial guess and, once per solve, of div
+    if ((rc = launch_zper_wrap(phi, nz, ny, nx, G, G, s)) || (rc = launch_zper_wrap(div, nz, ny, nx, G, G, s)))
+        return rc;
+    const int tk = timing_begin(s);
+    const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
+    const bool m2_ok = !mask2d || ((reinterpret_cast<uintptr_t>(mask2d) & 3u) == 0 &&
+                                   rbgs3d_tbr_mask_ok(P, rbgs3d_half_rows(P)) &&
+                                   (H % P == 0 || rbgs3d_tbr_mask_ok(H % P, rbgs3d_half_rows(H % P))));
+    if (m2_ok && rbgs3d_fused_ok(phi, phi_tmp, div, nullptr, nx)) {
+        // rows 0 and ny - 1 of every plane, ghosts included, in the other buffer
+        if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, nzt, -1, -1, s))) return rc;
+        float *a = phi, *b = phi_tmp;
+        for (int h = 0; h < H; h += P) {
+            const int m = H - h >= P ? P : H - h;
+            if ((rc = rbgs3d_half_pass(a, b, div, nzt, ny, nx, zb, ze, 0, 0, zoff, k, h, m, w, s, 0, mask2d)))
+                return rc;
+            // the ghosts of the buffer just written (a skipped pass: a copy
+            // inside a stale buffer, of the values its ghosts hold already)
+            if ((rc = launch_zper_wrap(b, nz, ny, nx, G, G, s))) return rc;
+            float *t = a; a = b; b = t;
+        }
+        const int hpp = P;
+        timing_end(tk, s, iterations);
+        if ((rc = launch_rbgs_count(w, iters_done, s))) return rc;
+        for (int need = 1; need < hpp && k.tol > 0.f; ++need)
+            if (!(hpp % 2 == 0 && need % 2 == 1) &&
+                (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, nzt, ny, nx, zb, ze, 0, 0, zoff, k, 0, need, w, hpp, H, 0,
+                                      s, 0, mask2d)))
+                return rc;
+        return launch_rbgs_copy(w, phi, phi_tmp, n, hpp, s);
+    }
+    for (int it = 0; it < iterations; ++it)
+        for (int colour = 0; colour < 2; ++colour)
+            if ((rc = rbgs3d_colour_pass(colour, phi, div, mask2d, ny, nx, zb, ze, zoff, k, w, it, s, true)) ||
+                (rc = launch_zper_wrap(phi, nz, ny, nx, G, 1, s)))
+                return rc;
+    timing_end(tk, s, iterations);
+    return launch_rbgs_finish(w, phi, nullptr, n, iters_done, s);
 }
 
 int cfd_rbgs3d_pass_f32(const float *in, float *out, const float *div, int nz, int ny, int nx,

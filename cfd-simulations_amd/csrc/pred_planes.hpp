@@ -36,6 +36,12 @@
 // advanced by k * ny * nx elements in 64 bits, one plane's bytes as the
 // range), so offsets stay below 2^31 on arrays of any size; a plane outside
 // the grid, or past the chunk's last U plane, gets an empty range and reads 0.
+//
+// ZPER (spanwise-periodic z): every plane is interior in z and the plane index
+// of a resource is taken modulo nz -- the first chunk preloads plane nz - 1 as
+// its D, the last chunk loads plane 0 as its U -- while the chunk-window test
+// stays on the unwrapped index.  A template parameter: the non-periodic
+// instantiations are the code they were.
 #pragma once
 #include "common.hpp"
 #include "pred_rows.hpp"
@@ -168,8 +174,9 @@ struct Plane {
     float halo[R];
 };
 
-template <int VEC, int R, bool SUPG, int NM = kNu3Scalar>
+template <int VEC, int R, bool SUPG, int NM = kNu3Scalar, bool ZPER = false>
 __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
+    static_assert(!ZPER || NM != kNu3Array, "periodic z: scalar and LES viscosity only");
     constexpr int SW = 64 * VEC;  // segment width (columns)
     const int lane = threadIdx.x & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -206,7 +213,8 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
     // plane z of a field as a buffer resource: an empty range outside
     // [max(z0 - 1, 0), min(z1, nz - 1)] (nothing there is ever used)
     auto prsrc = [&](const float *base, int z) {
-        const bool in = z >= 0 && z < nz && z >= z0 - 1 && z <= z1;
+        const bool in = (ZPER || (z >= 0 && z < nz)) && z >= z0 - 1 && z <= z1;
+        if constexpr (ZPER) z = z < 0 ? z + nz : (z >= nz ? z - nz : z);  // -1 .. nz only (the window)
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base) + (in ? (size_t)z * plane : 0), 0,
                                                  in ? pbytes : 0, 0x00020000);
     };
@@ -250,7 +258,7 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
         }
         // two planes ahead
         const Plane<VEC, R> Un = load_plane(a.u, z + 2), Vn = load_plane(a.v, z + 2), Wn = load_plane(a.w, z + 2);
-        const bool zin = z >= 1 && z <= nz - 2;  // wave-uniform
+        const bool zin = ZPER || (z >= 1 && z <= nz - 2);  // wave-uniform
         const size_t pofs = (size_t)z * plane;
         const __amdgpu_buffer_rsrc_t rus = __builtin_amdgcn_make_buffer_rsrc(a.us + pofs, 0, pbytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rvs = __builtin_amdgcn_make_buffer_rsrc(a.vs + pofs, 0, pbytes, 0x00020000);
@@ -338,30 +346,36 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
     }
 }
 
-template <int VEC, int R, int NM>
+template <int VEC, int R, int NM, bool ZPER = false>
 inline const void *pred_planes_kernel_nm(bool supg) {
-    return supg ? (const void *)k_predictor3d_planes<VEC, R, true, NM>
-                : (const void *)k_predictor3d_planes<VEC, R, false, NM>;
+    return supg ? (const void *)k_predictor3d_planes<VEC, R, true, NM, ZPER>
+                : (const void *)k_predictor3d_planes<VEC, R, false, NM, ZPER>;
 }
 template <int VEC, int R>
-inline const void *pred_planes_kernel(bool supg, int nm) {
+inline const void *pred_planes_kernel(bool supg, int nm, bool zper) {
+    if (zper)  // scalar and LES only (the caller has no periodic array mode)
+        return nm == kNu3Les ? pred_planes_kernel_nm<VEC, R, kNu3Les, true>(supg)
+                             : pred_planes_kernel_nm<VEC, R, kNu3Scalar, true>(supg);
     if (nm == kNu3Array) return pred_planes_kernel_nm<VEC, R, kNu3Array>(supg);
     if (nm == kNu3Les) return pred_planes_kernel_nm<VEC, R, kNu3Les>(supg);
     return pred_planes_kernel_nm<VEC, R, kNu3Scalar>(supg);
 }
 
 // Plane-march launch: cells per lane vec (1, 2, 4), rows per wave rows (1, 2),
-// planes per chunk zchunk (0: auto); a.nseg / a.ntile / a.zchunk are filled
-// here.  The caller has checked shape (a plane below 2^31 bytes, nx % vec == 0)
-// and alignment.
-inline hipError_t pred_planes_launch(Pred3Args a, bool supg, int nm, int vec, int rows, int zchunk, hipStream_t s) {
+// planes per chunk zchunk (0: auto), zper: periodic z (not with kNu3Array);
+// a.nseg / a.ntile / a.zchunk are filled here.  The caller has checked shape
+// (a plane below 2^31 bytes, nx % vec == 0) and alignment.
+inline hipError_t pred_planes_launch(Pred3Args a, bool supg, int nm, int vec, int rows, int zchunk, hipStream_t s,
+                                     bool zper = false) {
     const void *f;
     if (rows == 1)
-        f = vec == 4 ? pred_planes_kernel<4, 1>(supg, nm)
-                     : (vec == 2 ? pred_planes_kernel<2, 1>(supg, nm) : pred_planes_kernel<1, 1>(supg, nm));
+        f = vec == 4   ? pred_planes_kernel<4, 1>(supg, nm, zper)
+            : vec == 2 ? pred_planes_kernel<2, 1>(supg, nm, zper)
+                       : pred_planes_kernel<1, 1>(supg, nm, zper);
     else
-        f = vec == 4 ? pred_planes_kernel<4, 2>(supg, nm)
-                     : (vec == 2 ? pred_planes_kernel<2, 2>(supg, nm) : pred_planes_kernel<1, 2>(supg, nm));
+        f = vec == 4   ? pred_planes_kernel<4, 2>(supg, nm, zper)
+            : vec == 2 ? pred_planes_kernel<2, 2>(supg, nm, zper)
+                       : pred_planes_kernel<1, 2>(supg, nm, zper);
     a.nseg = ceil_div(a.nx, 64 * vec);
     a.ntile = ceil_div(a.ny, 4 * rows);
     // planes per chunk: each chunk re-reads 2 planes, so long chunks, but at

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ._lib import call, ptr, stream_handle, lib
+from ._lib import CfdError, call, ptr, stream_handle, lib
 
 __all__ = [
     "compute_convection_fast", "compute_convection_supg_fast", "compute_supg_stabilization_fast",
@@ -26,7 +26,7 @@ __all__ = [
     "solve_pressure_gauss_seidel3d", "persistent_failures",
     "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
     "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
-    "apply_channel_bc_ibm3d", "compute_vorticity3d",
+    "apply_channel_bc_ibm3d", "compute_vorticity3d", "solve_pressure_gauss_seidel3d_zper",
 ]
 
 
@@ -295,6 +295,38 @@ def solve_pressure_gauss_seidel3d(phi, div, dx, dy, dz, dt, mask, iterations, to
     return phi
 
 
+def solve_pressure_gauss_seidel3d_zper(phi_pad, div_pad, dx, dy, dz, dt, mask2d, iterations, tolerance,
+                                       workspace=None, iters_done=None, phi_tmp=None, nz=None):
+    """solve_pressure_gauss_seidel3d with a periodic z (cfd_rbgs3d_zper_f32):
+    all nz planes are updated, plane nz-1's U neighbour is plane 0; nz even
+    and >= 4.  ``phi_pad``, ``div_pad`` and ``phi_tmp`` are (nz + 2G, ny, nx)
+    with G = cfd_rbgs3d_zper_ghost(); the caller fills planes G .. G+nz-1
+    (``phi_pad[G:G+nz]`` is the solution afterwards), the ghost planes of all
+    three are the solver's and ``div_pad``'s are written.  ``mask2d``: None or
+    the (ny, nx) solid mask of every plane.  ``nz``: the number of periodic
+    planes (default: phi_pad's planes minus 2G); arrays that are not padded to
+    it raise CfdError.  Without ``phi_tmp`` the solve runs in-place colour
+    passes (the same bits).  Returns phi_pad."""
+    G = int(lib().cfd_rbgs3d_zper_ghost())
+    nzt, ny, nx = _shape3d(_f32(phi_pad, "phi_pad"))
+    nz = nzt - 2 * G if nz is None else int(nz)
+    for name, t in (("phi_pad", phi_pad), ("div_pad", div_pad), ("phi_tmp", phi_tmp)):
+        if t is not None and (tuple(t.shape) != (nz + 2 * G, ny, nx) or t.dtype != torch.float32
+                              or t.device != phi_pad.device):
+            raise CfdError(f"solve_pressure_gauss_seidel3d_zper: {name} must be a float32 ({nz + 2 * G}, {ny}, {nx}) "
+                           f"array (nz = {nz} planes plus {G} ghost planes at each end) on {phi_pad.device}, "
+                           f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+    m = _mask_u8(mask2d, (ny, nx))
+    need = int(lib().cfd_rbgs_workspace_bytes(int(iterations)))
+    ws = workspace
+    if ws is None or ws.numel() * ws.element_size() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=phi_pad.device)
+    call("cfd_rbgs3d_zper_f32", ptr(phi_pad), ptr(_f32(div_pad, "div_pad")), ptr(m), nz, ny, nx, float(dx),
+         float(dy), float(dz), float(np.float32(dt)), int(iterations), float(tolerance), ptr(phi_tmp), ptr(ws),
+         ptr(iters_done), stream_handle())
+    return phi_pad
+
+
 def apply_ibm_fast(u, v, ibm_mask, force_strength):
     """v5.py:228-237, in place; ``ibm_mask`` is the float64 mask. Returns (u, v)."""
     if ibm_mask.dtype != torch.float64:
@@ -416,26 +448,31 @@ def _fields3d(model, /, **others):
 
 
 def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=None, v_star=None, w_star=None,
-                      tau=None, store_tau=True):
+                      tau=None, store_tau=True, periodic_z=False):
     """The 3-D fused predictor (cfd_predictor3d_f32): SUPG tau, convection and
     Laplacian of u, v, w and f_star = f + dt*(-conv + lap) in one pass, the six
     faces copied through.  ``nu_eff`` is a scalar, or a tensor of the fields'
     shape read per cell (cfd_predictor3d_nu_f32).  Returns (u_star, v_star,
     w_star, tau); arrays not given are allocated.  ``store_tau=False`` with no
     ``tau`` given: tau is not stored (24 B per cell instead of 28) and None is
-    returned for it.  Without SUPG a stored tau is zeros."""
+    returned for it.  Without SUPG a stored tau is zeros.  ``periodic_z``:
+    every plane is interior in z and plane nz-1's U neighbour is plane 0
+    (cfd_predictor3d_zper_f32; scalar ``nu_eff`` only)."""
     us = torch.empty_like(u) if u_star is None else u_star
     vs = torch.empty_like(u) if v_star is None else v_star
     ws = torch.empty_like(u) if w_star is None else w_star
     if tau is None and store_tau:
         tau = torch.empty_like(u)
     if isinstance(nu_eff, torch.Tensor) and nu_eff.dim() > 0:
+        if periodic_z:
+            raise ValueError("predictor3d_fused: periodic_z takes a scalar nu_eff (LES: predictor3d_fused_les)")
         nz, ny, nx = _fields3d(u, v=v, w=w, nu_eff=nu_eff, u_star=us, v_star=vs, w_star=ws, tau=tau)
         call("cfd_predictor3d_nu_f32", ptr(u), ptr(v), ptr(w), ptr(nu_eff), ptr(us), ptr(vs), ptr(ws), ptr(tau),
              nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle())
         return us, vs, ws, tau
     nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau)
-    call("cfd_predictor3d_f32", ptr(u), ptr(v), ptr(w), float(np.float32(nu_eff)), ptr(us), ptr(vs), ptr(ws),
+    call("cfd_predictor3d_zper_f32" if periodic_z else "cfd_predictor3d_f32", ptr(u), ptr(v), ptr(w),
+         float(np.float32(nu_eff)), ptr(us), ptr(vs), ptr(ws),
          ptr(tau), nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)),
          stream_handle())
     return us, vs, ws, tau
@@ -456,14 +493,15 @@ def compute_smagorinsky_viscosity3d(u, v, w, dx, dy, dz, cs, out=None):
 
 
 def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=True, u_star=None, v_star=None,
-                          w_star=None, tau=None, nu_t=None, store_tau=True, store_nu_t=True):
+                          w_star=None, tau=None, nu_t=None, store_tau=True, store_nu_t=True, periodic_z=False):
     """The 3-D LES predictor (cfd_predictor3d_les_f32) in one pass: nu_t =
     compute_smagorinsky_viscosity3d(u, v, w, ...), nu_eff = (nu + nu_t) +
     art_visc per cell in float32, then predictor3d_fused with that array --
     the same bits as those calls, with nu_t formed from the values the kernel
     holds anyway.  Returns (u_star, v_star, w_star, tau, nu_t); arrays not
     given are allocated, unless ``store_tau`` / ``store_nu_t`` is False: that
-    array is then not stored and None is returned for it."""
+    array is then not stored and None is returned for it.  ``periodic_z``: as
+    in predictor3d_fused (cfd_predictor3d_les_zper_f32; nu_t on all planes)."""
     us = torch.empty_like(u) if u_star is None else u_star
     vs = torch.empty_like(u) if v_star is None else v_star
     ws = torch.empty_like(u) if w_star is None else w_star
@@ -472,37 +510,43 @@ def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=Tr
     if nu_t is None and store_nu_t:
         nu_t = torch.empty_like(u)
     nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau, nu_t=nu_t)
-    call("cfd_predictor3d_les_f32", ptr(u), ptr(v), ptr(w), float(np.float32(nu)), float(np.float32(art_visc)),
+    call("cfd_predictor3d_les_zper_f32" if periodic_z else "cfd_predictor3d_les_f32", ptr(u), ptr(v), ptr(w),
+         float(np.float32(nu)), float(np.float32(art_visc)),
          float(cs), ptr(us), ptr(vs), ptr(ws), ptr(tau), ptr(nu_t), nz, ny, nx, float(dx), float(dy), float(dz),
          _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle())
     return us, vs, ws, tau, nu_t
 
 
-def compute_divergence3d(u, v, w, dx, dy, dz, out=None, absmax=None):
+def compute_divergence3d(u, v, w, dx, dy, dz, out=None, absmax=None, periodic_z=False):
     """div = ((uE-uW) cx + (vN-vS) cy) + (wU-wD) cz, 0 on the six faces.
     ``absmax``: optional zeroed float32 device scalar that receives max|div|
-    without a host sync.  Returns div (``out`` if given)."""
+    without a host sync.  ``periodic_z``: z wraps and only the four x / y
+    faces are 0 (cfd_divergence3d_zper_f32).  Returns div (``out`` if given)."""
     div = torch.empty_like(u) if out is None else out
     nz, ny, nx = _fields3d(u, v=v, w=w, div=div)
     if absmax is not None:
         _f32(absmax, "absmax")
-    call("cfd_divergence3d_f32", ptr(u), ptr(v), ptr(w), ptr(div), nz, ny, nx, float(dx), float(dy), float(dz),
-         ptr(absmax), stream_handle())
+    call("cfd_divergence3d_zper_f32" if periodic_z else "cfd_divergence3d_f32", ptr(u), ptr(v), ptr(w), ptr(div),
+         nz, ny, nx, float(dx), float(dy), float(dz), ptr(absmax), stream_handle())
     return div
 
 
-def project_velocity3d(phi, u_star, v_star, w_star, dx, dy, dz, dt, u=None, v=None, w=None, gradmax=None):
+def project_velocity3d(phi, u_star, v_star, w_star, dx, dy, dz, dt, u=None, v=None, w=None, gradmax=None,
+                       periodic_z=False):
     """u = u* - dt dphi/dx, v = v* - dt dphi/dy, w = w* - dt dphi/dz on the
     interior, the faces copied through.  ``gradmax``: optional zeroed float32
-    device scalar for max|grad phi|.  Returns (u, v, w)."""
+    device scalar for max|grad phi|.  ``periodic_z``: z wraps and only the
+    four x / y faces are copied through (cfd_project3d_zper_f32).  Returns
+    (u, v, w)."""
     u = torch.empty_like(phi) if u is None else u
     v = torch.empty_like(phi) if v is None else v
     w = torch.empty_like(phi) if w is None else w
     nz, ny, nx = _fields3d(phi, u_star=u_star, v_star=v_star, w_star=w_star, u=u, v=v, w=w)
     if gradmax is not None:
         _f32(gradmax, "gradmax")
-    call("cfd_project3d_f32", ptr(phi), ptr(u_star), ptr(v_star), ptr(w_star), ptr(u), ptr(v), ptr(w), nz, ny, nx,
-         float(dx), float(dy), float(dz), _dt_arg(dt, phi.dtype), ptr(gradmax), stream_handle())
+    call("cfd_project3d_zper_f32" if periodic_z else "cfd_project3d_f32", ptr(phi), ptr(u_star), ptr(v_star),
+         ptr(w_star), ptr(u), ptr(v), ptr(w), nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, phi.dtype),
+         ptr(gradmax), stream_handle())
     return u, v, w
 
 
@@ -514,7 +558,8 @@ def apply_lid_bc3d(u, v, w, u_lid):
     return u, v, w
 
 
-def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_strength, bbox=None, force_out=None):
+def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_strength, bbox=None, force_out=None,
+                           periodic_z=False):
     """The cylinder channel's boundary conditions and immersed-boundary forcing
     in place on (nz, ny, nx) float32 u, v, w, one launch
     (cfd_apply_channel_bc_ibm3d_f32): inlet column (``y``: the float64 row
@@ -525,7 +570,9 @@ def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_str
     every m > 0 (None: the whole plane); only that box is visited for the
     forcing.  ``force_out``: optional float64 device tensor of 3 elements,
     accumulated into (zero it first): the sums of before - after of u, v, w
-    over the forced cells.  Returns (u, v, w)."""
+    over the forced cells.  ``periodic_z``: no spanwise faces -- the other
+    assignments on every plane (cfd_apply_channel_bc_ibm3d_zper_f32).
+    Returns (u, v, w)."""
     nz, ny, nx = _fields3d(u, v=v, w=w)
     if y.dtype != torch.float64 or y.numel() != ny:
         raise ValueError(f"y must be {ny} float64 row coordinates, got {tuple(y.shape)} {y.dtype}")
@@ -535,25 +582,29 @@ def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_str
     if force_out is not None and (force_out.dtype != torch.float64 or force_out.numel() != 3):
         raise ValueError("force_out must be three float64 elements")
     i0, i1, j0, j1 = (0, ny, 0, nx) if bbox is None else (int(b) for b in bbox)
-    call("cfd_apply_channel_bc_ibm3d_f32", ptr(u), ptr(v), ptr(w), ptr(y), ptr(ibm_mask2d), nz, ny, nx, float(y_max),
-         float(v_inf), int(step), float(force_strength), i0, i1, j0, j1, ptr(force_out), stream_handle())
+    call("cfd_apply_channel_bc_ibm3d_zper_f32" if periodic_z else "cfd_apply_channel_bc_ibm3d_f32", ptr(u), ptr(v),
+         ptr(w), ptr(y), ptr(ibm_mask2d), nz, ny, nx, float(y_max), float(v_inf), int(step), float(force_strength),
+         i0, i1, j0, j1, ptr(force_out), stream_handle())
     return u, v, w
 
 
-def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax=None):
+def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax=None, periodic_z=False):
     """The vorticity magnitude of (nz, ny, nx) float32 u, v, w
     (cfd_vorticity3d_f32): central differences on the interior, 0 on the six
     faces, NaN where the (nz, ny, nx) ``mask`` is set.  Returns mag, or
     (ox, oy, oz, mag) with ``components=True``.  ``absmax``: optional zeroed
-    float32 device scalar that receives nanmax(mag) without a host sync."""
+    float32 device scalar that receives nanmax(mag) without a host sync.
+    ``periodic_z``: z wraps and only the four x / y faces are 0
+    (cfd_vorticity3d_zper_f32)."""
     mag = torch.empty_like(u)
     nz, ny, nx = _fields3d(u, v=v, w=w)
     comp = [torch.empty_like(u) for _ in range(3)] if components else [None] * 3
     if absmax is not None:
         _f32(absmax, "absmax")
     m = _mask_u8(mask, u.shape)
-    call("cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w), ptr(m), ptr(comp[0]), ptr(comp[1]),
-         ptr(comp[2]), ptr(mag), ptr(absmax), nz, ny, nx, float(dx), float(dy), float(dz), stream_handle())
+    call("cfd_vorticity3d_zper_f32" if periodic_z else "cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w), ptr(m),
+         ptr(comp[0]), ptr(comp[1]), ptr(comp[2]), ptr(mag), ptr(absmax), nz, ny, nx, float(dx), float(dy), float(dz),
+         stream_handle())
     return (comp[0], comp[1], comp[2], mag) if components else mag
 
 

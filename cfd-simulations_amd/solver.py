@@ -572,6 +572,8 @@ class LidDrivenCavity3DSolver:
     slab-decomposed (multi-GPU) step, and the 2-D step's clean_divergence
     stage (a v5 quirk with serial semantics that does not generalise)."""
 
+    _periodic_z = False  # CylinderChannel3DSolver with spanwise_bc="periodic": the *_zper stages
+
     def __init__(self, config: LidDrivenCavity3DConfig):
         self.config = cfg = config
         self.dtype = torch.float32
@@ -690,18 +692,20 @@ class LidDrivenCavity3DSolver:
             # nu_eff = (nu + nu_t) + art_visc per cell in float32
             K.predictor3d_fused_les(self.u, self.v, self.w, *sp, dt, cfg.nu, cfg.artificial_viscosity,
                                     cfg.smagorinsky_constant, cfg.use_supg, u_star=self.u_star,
-                                    v_star=self.v_star, w_star=self.w_star, nu_t=self.nu_t, store_tau=False)
+                                    v_star=self.v_star, w_star=self.w_star, nu_t=self.nu_t, store_tau=False,
+                                    periodic_z=self._periodic_z)
         else:
             # nu_eff = (nu + 0) + art_visc in float32, a scalar
             nu_eff = np.float32(np.float32(cfg.nu) + np.float32(0.0)) + np.float32(cfg.artificial_viscosity)
             K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
-                                v_star=self.v_star, w_star=self.w_star, store_tau=False)
+                                v_star=self.v_star, w_star=self.w_star, store_tau=False,
+                                periodic_z=self._periodic_z)
         self.apply_boundary_conditions(self.u_star, self.v_star, self.w_star)
         K.compute_divergence3d(self.u_star, self.v_star, self.w_star, *sp, out=self.div_u_star,
-                               absmax=self._scal[1:2] if diag else None)
+                               absmax=self._scal[1:2] if diag else None, periodic_z=self._periodic_z)
         self.solve_pressure_fast(self.div_u_star)
         K.project_velocity3d(self.phi, self.u_star, self.v_star, self.w_star, *sp, dt, u=self.u, v=self.v, w=self.w,
-                             gradmax=self._scal[2:3] if diag else None)
+                             gradmax=self._scal[2:3] if diag else None, periodic_z=self._periodic_z)
         self.apply_boundary_conditions(self.u, self.v, self.w)
         # the energy of the unclipped fields, then the three clips, one launch
         call("cfd_energy_mean_clip3d_f32", ptr(self.u), ptr(self.v), ptr(self.w), self.u.numel(),
@@ -721,7 +725,15 @@ class CylinderChannel3DConfig(OptimizedTurbulentConfig):
     axis is along z.  200 iterations per pressure solve, as in the 3-D cavity.
     use_les=True forms the 3-D Smagorinsky eddy viscosity (constant 0.17)
     inside the predictor; False (the default) ignores the constant.  float32
-    only."""
+    only.
+
+    spanwise_bc: "free_slip" (the default: planes 0 and nz-1 are free-slip
+    walls, dz = (z_max - z_min) / (nz - 1)) or "periodic" (all nz planes are
+    interior in z and plane nz-1's neighbour is plane 0; dz = (z_max - z_min)
+    / nz, nz even and >= 4, red-black GS only).  spanwise_perturbation = a:
+    the initial u of plane k is scaled by 1 + a cos(2 pi (z_k - z_min) / (z_max
+    - z_min)), the one thing that makes the flow depend on z; 0.0 (the
+    default) is the z-invariant start."""
     z_min: float = 0.0
     z_max: float = 4.0
     nz: int = 120
@@ -729,10 +741,24 @@ class CylinderChannel3DConfig(OptimizedTurbulentConfig):
     smagorinsky_constant: float = 0.17
     output_dir: str = "cylinder3d_re_600"
     hdf5_file: str = "cylinder3d_re_600.h5"
+    spanwise_bc: str = "free_slip"
+    spanwise_perturbation: float = 0.0
 
     def __post_init__(self):
         super().__post_init__()
-        self.dz = (self.z_max - self.z_min) / (self.nz - 1)
+        if self.spanwise_bc not in ("free_slip", "periodic"):
+            raise ValueError(f"CylinderChannel3DConfig: spanwise_bc must be 'free_slip' or 'periodic', "
+                             f"not {self.spanwise_bc!r}")
+        if self.spanwise_bc == "periodic":
+            if self.nz < 4 or self.nz % 2:
+                raise ValueError(f"CylinderChannel3DConfig: periodic spanwise boundaries need an even nz >= 4 "
+                                 f"(got {self.nz}): the two planes of a wrap must have opposite red-black parity")
+            if not self.use_fast_pressure:
+                raise ValueError("CylinderChannel3DConfig: periodic spanwise boundaries need the red-black GS "
+                                 "(use_fast_pressure=True): the blocked and masked Jacobi has no periodic form")
+            self.dz = (self.z_max - self.z_min) / self.nz
+        else:
+            self.dz = (self.z_max - self.z_min) / (self.nz - 1)
         if not self.memory_efficient:
             raise ValueError("CylinderChannel3DConfig: the 3-D step is float32 only (memory_efficient=True)")
 
@@ -774,15 +800,35 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     |omega| (NaN in the cylinder); with log_diagnostics ``diagnostics`` gains
     ``vorticity_max`` of the step's final unclipped fields.
 
+    spanwise_bc="periodic": every stage is its *_zper form (the pad rule:
+    the operator on the field with plane nz-1 put in front and plane 0 behind,
+    cropped; tests/zper_reference.py), the boundary stage loses its face
+    step, ``z`` = z_min + k dz with dz = Lz / nz, and the pressure solve is
+    cfd_rbgs3d_zper_f32 on arrays padded by its ghost planes -- ``phi`` and
+    ``div_u_star`` are the (nz, ny, nx) views of the owned planes.
+    spanwise_perturbation (either spanwise_bc) scales the initial u per plane,
+    which is what makes a run three-dimensional.
+
     Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
-    single sweeps: DESIGN.md 4.4), masks that vary along z in the fused GS,
-    periodic spanwise boundaries, snapshots, float64 and the slab path."""
+    single sweeps: DESIGN.md 4.4), a periodic form of that Jacobi, masks that
+    vary along z in the fused GS, snapshots, float64 and the slab path."""
 
     def __init__(self, config: CylinderChannel3DConfig):
         super().__init__(config)
         cfg = config
         self.x, self.y, self.X, self.Y = host_grid(cfg)
-        self.z = np.linspace(cfg.z_min, cfg.z_max, cfg.nz)
+        self._periodic_z = cfg.spanwise_bc == "periodic"
+        if self._periodic_z:
+            self.z = cfg.z_min + np.arange(cfg.nz) * cfg.dz
+            # the solve's arrays with its ghost planes; phi and div_u_star are the owned planes
+            G = int(lib().cfd_rbgs3d_zper_ghost())
+            pad = lambda: torch.zeros((cfg.nz + 2 * G, cfg.ny, cfg.nx), dtype=self.dtype,  # noqa: E731
+                                      device=self.device)
+            self._phi_pad, self._div_pad, self._phi_tmp = pad(), pad(), pad()
+            self.phi, self.div_u_star = self._phi_pad[G:G + cfg.nz], self._div_pad[G:G + cfg.nz]
+            self._rhs_ws = None  # the Jacobi's workspace: no periodic form
+        else:
+            self.z = np.linspace(cfg.z_min, cfg.z_max, cfg.nz)
         self._y_dev = torch.from_numpy(self.y).to(self.device)
         self.dist, cyl, ibm = host_masks(cfg, self.X, self.Y)
         self.cylinder_mask_host, self.ibm_mask_host = cyl, ibm
@@ -791,7 +837,13 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         self.cylinder_mask2d = torch.from_numpy(cyl).to(self.device).to(torch.uint8).contiguous()
         self.cylinder_mask = self.cylinder_mask2d.expand(cfg.nz, cfg.ny, cfg.nx).contiguous()
         u, v = host_potential_flow(cfg, self.X, self.Y, self.dist, ibm, np.float32)
-        self.u.copy_(torch.from_numpy(u).to(self.device).expand_as(self.u))
+        if cfg.spanwise_perturbation != 0.0:
+            # u[k] = f32(f64(u2d) (1 + a cos(2 pi (z_k - z_min) / Lz))), host side, one time
+            ph = 2.0 * np.pi * (self.z - cfg.z_min) / (cfg.z_max - cfg.z_min)
+            u3 = (u.astype(np.float64)[None] * (1.0 + cfg.spanwise_perturbation * np.cos(ph))[:, None, None])
+            self.u.copy_(torch.from_numpy(u3.astype(np.float32)).to(self.device))
+        else:
+            self.u.copy_(torch.from_numpy(u).to(self.device).expand_as(self.u))
         self.v.copy_(torch.from_numpy(v).to(self.device).expand_as(self.v))
         self._force = torch.zeros((1024, 3), dtype=torch.float64, device=self.device)
         self._dts = []
@@ -804,6 +856,13 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         if not cfg.use_fast_pressure and not (cfg.dx == cfg.dy == cfg.dz):
             raise ValueError(f"the 3-D Jacobi solve needs dx == dy == dz (got {cfg.dx}, {cfg.dy}, {cfg.dz}); "
                              "use_fast_pressure=True takes any spacing")
+        if self._periodic_z:  # div_u_star is the owned planes of _div_pad
+            self._phi_pad.zero_()
+            K.solve_pressure_gauss_seidel3d_zper(self._phi_pad, self._div_pad, cfg.dx, cfg.dy, cfg.dz, cfg.dt,
+                                                 self.cylinder_mask2d, cfg.pressure_iterations,
+                                                 cfg.pressure_tolerance, workspace=self._gs_ws,
+                                                 iters_done=self._gs_done, phi_tmp=self._phi_tmp, nz=cfg.nz)
+            return self.phi
         self.phi.zero_()
         if cfg.use_fast_pressure:
             K.solve_pressure_gauss_seidel3d(self.phi, div_u_star, cfg.dx, cfg.dy, cfg.dz, cfg.dt,
@@ -830,11 +889,11 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         final = u is self.u
         K.apply_channel_bc_ibm3d(u, v, w, self._y_dev, self.ibm_mask, cfg.y_max, cfg.V_inf, self.step,
                                  min(1.0, self.step / cfg.initial_steps), bbox=self.ibm_bbox,
-                                 force_out=self._force_slot() if final else None)
+                                 force_out=self._force_slot() if final else None, periodic_z=self._periodic_z)
         if final and cfg.log_diagnostics:
             self._scal[3:4].zero_()
-            call("cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w), ptr(self.cylinder_mask), None, None, None, None,
-                 ptr(self._scal[3:4]), cfg.nz, cfg.ny, cfg.nx, float(cfg.dx), float(cfg.dy), float(cfg.dz),
+            call("cfd_vorticity3d_zper_f32" if self._periodic_z else "cfd_vorticity3d_f32", ptr(u), ptr(v), ptr(w),
+                 ptr(self.cylinder_mask), None, None, None, None, ptr(self._scal[3:4]), cfg.nz, cfg.ny, cfg.nx, float(cfg.dx), float(cfg.dy), float(cfg.dz),
                  stream_handle())
 
     def time_step(self):
@@ -843,9 +902,11 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         return dt
 
     def compute_vorticity(self):
-        """|omega| of the current fields: 0 on the six faces, NaN in the cylinder."""
+        """|omega| of the current fields: 0 on the six faces (periodic: the
+        four x / y faces), NaN in the cylinder."""
         cfg = self.config
-        return K.compute_vorticity3d(self.u, self.v, self.w, cfg.dx, cfg.dy, cfg.dz, mask=self.cylinder_mask)
+        return K.compute_vorticity3d(self.u, self.v, self.w, cfg.dx, cfg.dy, cfg.dz, mask=self.cylinder_mask,
+                                     periodic_z=self._periodic_z)
 
     @property
     def diagnostics(self):
@@ -883,7 +944,8 @@ def monitor_simulation_health3d(solver: LidDrivenCavity3DSolver, step: int) -> b
     """monitor_simulation_health's thresholds (v5.py:599-613) on u, v, w
     (LidDrivenCavity3DSolver or CylinderChannel3DSolver):
     non-finite values, max|V| > max_velocity, max|div| above 20 (step <= 1000)
-    or 2 (after); device reductions with one host read."""
+    or 2 (after); device reductions with one host read.  A spanwise-periodic
+    solver's divergence is the periodic one."""
     cfg = solver.config
     s = stream_handle()
     n = solver.u.numel()
@@ -894,7 +956,8 @@ def monitor_simulation_health3d(solver: LidDrivenCavity3DSolver, step: int) -> b
     for f in (solver.u, solver.v, solver.w):
         call("cfd_absmax_f32", ptr(f), n, ptr(red[0:1]), s)  # the max accumulates
     div = torch.empty_like(solver.u)
-    call("cfd_divergence3d_f32", ptr(solver.u), ptr(solver.v), ptr(solver.w), ptr(div), cfg.nz, cfg.ny, cfg.nx,
+    call("cfd_divergence3d_zper_f32" if solver._periodic_z else "cfd_divergence3d_f32", ptr(solver.u),
+         ptr(solver.v), ptr(solver.w), ptr(div), cfg.nz, cfg.ny, cfg.nx,
          float(cfg.dx), float(cfg.dy), float(cfg.dz), ptr(red[1:2]), s)
     n_bad = int(cnt.sum().item())
     vel_max, div_max = (float(x) for x in red.cpu().numpy())

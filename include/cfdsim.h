@@ -178,6 +178,30 @@ int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, in
 int cfd_rbgs3d_mask2d_f32(float *phi, const float *div, const uint8_t *mask2d, int nz, int ny, int nx,
                           double dx, double dy, double dz, float dt, int iterations, double tolerance,
                           float *phi_tmp, void *ws, int *iters_done, void *stream);
+/* Ghost depth G of cfd_rbgs3d_zper_f32's arrays: 4, whatever the tuning. */
+int cfd_rbgs3d_zper_ghost(void);
+/* cfd_rbgs3d_mask2d_f32 with a periodic z: all nz planes are updated, the U
+ * neighbour of plane nz-1 is plane 0 and the D neighbour of plane 0 is plane
+ * nz-1; the colour of a cell is (z + i + j + 1 + colour) even as before, so
+ * nz must be even (the two planes of a wrap then have opposite parity) and at
+ * least 4: anything else is CFD_E_INVALID before any launch.  The x / y faces
+ * keep their values; max|change| and the stop rule are cfd_rbgs3d_f32's, over
+ * the nz planes.  Layout (cfd_slab_rbgs3d_f32's): phi, phi_tmp and div are
+ * (nz + 2G, ny, nx) with G = cfd_rbgs3d_zper_ghost(), the nz planes at
+ * G .. G+nz-1.  The caller fills those planes only; the function fills every
+ * ghost plane itself (div's once per solve: div is written to), and what the
+ * ghost planes hold afterwards is unspecified.  Fused under
+ * cfd_rbgs3d_mask2d_f32's conditions: tall-tile passes over planes [G, G+nz)
+ * with both ends non-fixed (the inner ghost planes' intermediate colours are
+ * recomputed), each followed by one launch that copies planes [G, 2G) to
+ * [G+nz, 2G+nz) and [nz, nz+G) to [0, G) of the buffer just written (float4
+ * per lane, streaming stores), so the pass work is (nz + 2G)/nz of the
+ * non-periodic solve's.  Otherwise (also: 3 levels with a mask) in-place
+ * colour passes over the nz planes with a one-plane wrap after each colour:
+ * the same bits.  mask2d may be NULL. */
+int cfd_rbgs3d_zper_f32(float *phi, float *div, const uint8_t *mask2d, int nz, int ny, int nx,
+                        double dx, double dy, double dz, float dt, int iterations, double tolerance,
+                        float *phi_tmp, void *ws, int *iters_done, void *stream);
 
 /* ---------------------------------------------------------------- predictor */
 
@@ -399,6 +423,26 @@ int cfd_predictor3d_les_f32(const float *u, const float *v, const float *w, floa
                             float art_visc, double cs, float *u_star, float *v_star,
                             float *w_star, float *tau, float *nu_t, int nz, int ny, int nx,
                             double dx, double dy, double dz, float dt, int use_supg, void *stream);
+/* cfd_predictor3d_f32 and cfd_predictor3d_les_f32 with a periodic z (the
+ * spanwise-periodic cylinder channel).  Pad rule, which defines every *_zper
+ * field operator: the result is the existing operator applied to the field
+ * with plane nz-1 put in front and plane 0 behind (nz + 2 planes), first and
+ * last plane dropped -- all nz planes are interior in z, the U neighbour of
+ * plane nz-1 is plane 0, the D neighbour of plane 0 is plane nz-1, and the
+ * four x / y faces behave as before.  tau and nu_t are formed on all planes.
+ * Both kernels wrap z: the plane march takes the plane index of a buffer
+ * resource modulo nz (a template parameter; the non-periodic instantiations
+ * are unchanged), the one-thread-per-cell kernel wraps its two z offsets.
+ * cfd_set_predictor3d_config and cfd_get_last_predictor3d_path apply. */
+int cfd_predictor3d_zper_f32(const float *u, const float *v, const float *w, float nu_eff,
+                             float *u_star, float *v_star, float *w_star, float *tau,
+                             int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                             int use_supg, void *stream);
+int cfd_predictor3d_les_zper_f32(const float *u, const float *v, const float *w, float nu,
+                                 float art_visc, double cs, float *u_star, float *v_star,
+                                 float *w_star, float *tau, float *nu_t, int nz, int ny, int nx,
+                                 double dx, double dy, double dz, float dt, int use_supg,
+                                 void *stream);
 /* Kernel of cfd_predictor3d_f32 / _nu_f32 / _les_f32 (tuning, per host
  * thread; the same bits either way; cfd_reset_tuning restores auto):
  * variant 0 = auto (the plane march --
@@ -423,6 +467,11 @@ int cfd_get_last_predictor3d_path(int *cells_per_lane);
 int cfd_divergence3d_f32(const float *u, const float *v, const float *w, float *div,
                          int nz, int ny, int nx, double dx, double dy, double dz,
                          float *absmax, void *stream);
+/* cfd_divergence3d_f32 with a periodic z (the pad rule of
+ * cfd_predictor3d_zper_f32): 0 on the four x / y faces only. */
+int cfd_divergence3d_zper_f32(const float *u, const float *v, const float *w, float *div,
+                              int nz, int ny, int nx, double dx, double dy, double dz,
+                              float *absmax, void *stream);
 /* Gradient + projection: gx = (phiE - phiW)*cx, gy = (phiN - phiS)*cy,
  * gz = (phiU - phiD)*cz, then u = u_star - dt*gx, v = v_star - dt*gy,
  * w = w_star - dt*gz on the interior; the six faces copy u_star, v_star,
@@ -432,6 +481,12 @@ int cfd_project3d_f32(const float *phi, const float *u_star, const float *v_star
                       const float *w_star, float *u, float *v, float *w,
                       int nz, int ny, int nx, double dx, double dy, double dz, float dt,
                       float *gradmax, void *stream);
+/* cfd_project3d_f32 with a periodic z (the pad rule): only the four x / y
+ * faces copy u_star, v_star, w_star through. */
+int cfd_project3d_zper_f32(const float *phi, const float *u_star, const float *v_star,
+                           const float *w_star, float *u, float *v, float *w,
+                           int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                           float *gradmax, void *stream);
 /* Lid-driven cavity walls in 3-D (the pattern of cfd_apply_lid_bc2d_f32):
  * u = v = w = 0 on all six faces, then u = u_lid, v = w = 0 on the face
  * y = ny - 1, written last: the lid owns its edges. */
@@ -476,6 +531,18 @@ int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y
                                    const double *ibm_mask2d, int nz, int ny, int nx, double y_max,
                                    double v_inf, int step, double force_strength, int i0, int i1,
                                    int j0, int j1, double *force_out, void *stream);
+/* cfd_apply_channel_bc_ibm3d_f32 for a periodic z: its assignments without
+ * step 3 (there are no face planes) -- inlet, outlet copy, channel walls
+ * written last, then the IBM factor, on every plane.  A cell (k, i, j') is
+ * written by the thread of (k, i, min(j', nx-2)); visited are the wall rows,
+ * the columns 0 and nx-2 and the clipped box, on all nz planes.  The box
+ * semantics, the one-writer rule, force_out and the order of its sum are
+ * cfd_apply_channel_bc_ibm3d_f32's. */
+int cfd_apply_channel_bc_ibm3d_zper_f32(float *u, float *v, float *w, const double *y,
+                                        const double *ibm_mask2d, int nz, int ny, int nx,
+                                        double y_max, double v_inf, int step, double force_strength,
+                                        int i0, int i1, int j0, int j1, double *force_out,
+                                        void *stream);
 /* The vorticity of u, v, w from central differences, with dx2 = f32(2*dx)
  * (likewise dy2, dz2) and the divisions of cfd_vorticity2d_f32:
  *   ox = (wN - wS)/dy2 - (vU - vD)/dz2,  oy = (uU - uD)/dz2 - (wE - wW)/dx2,
@@ -487,6 +554,11 @@ int cfd_apply_channel_bc_ibm3d_f32(float *u, float *v, float *w, const double *y
 int cfd_vorticity3d_f32(const float *u, const float *v, const float *w, const uint8_t *mask,
                         float *ox, float *oy, float *oz, float *mag, float *absmax,
                         int nz, int ny, int nx, double dx, double dy, double dz, void *stream);
+/* cfd_vorticity3d_f32 with a periodic z (the pad rule): 0 on the four x / y
+ * faces only. */
+int cfd_vorticity3d_zper_f32(const float *u, const float *v, const float *w, const uint8_t *mask,
+                             float *ox, float *oy, float *oz, float *mag, float *absmax,
+                             int nz, int ny, int nx, double dx, double dy, double dz, void *stream);
 
 /* --------------------------------------------------- float64 fields */
 /* memory_efficient=False (v5.py:287-296): every field float64; the kernels

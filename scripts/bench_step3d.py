@@ -34,8 +34,12 @@ red-black GS iterations at tolerance 0, alternating window by window: (a)
 cfd_rbgs3d_mask2d_f32 with the 2-D mask at 4 (auto) and at 2 half-sweeps per
 pass, (b) cfd_rbgs3d_f32 with the mask expanded to 3-D (in-place colour
 passes), (c) cfd_rbgs3d_f32 without a mask (the fused kernel's ceiling on this
-grid) -- then CylinderChannel3DSolver.time_step with the red-black GS, LES off
-and on, with the pressure solve's share of it.
+grid), (p) cfd_rbgs3d_zper_f32, the spanwise-periodic solve with the 2-D mask
+on its ghost-padded arrays -- then CylinderChannel3DSolver.time_step with the
+red-black GS, LES off and on, with the pressure solve's share of it; then the
+periodic leg: the fused predictor with and without periodic_z on the same
+fields (scalar and LES) and time_step with spanwise_bc "free_slip" and
+"periodic", each pair alternating window by window (medians of the rounds).
 
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
@@ -333,11 +337,20 @@ def cylinder_solves(s, rounds, iters=200):
     div = torch.randn((c.nz, c.ny, c.nx), device="cuda", generator=g) * 1e-3
     phi, tmp = torch.zeros_like(div), torch.empty_like(div)
     legs = {"a_mask2d": (s.cylinder_mask2d, 0), "a_mask2d_2_levels": (s.cylinder_mask2d, 2),
-            "b_mask3d": (s.cylinder_mask, 0), "c_unmasked": (None, 0)}
+            "b_mask3d": (s.cylinder_mask, 0), "c_unmasked": (None, 0), "p_mask2d_zper": (s.cylinder_mask2d, 0)}
+    # the periodic solve's arrays: the same div on the owned planes of the ghost-padded layout
+    G = int(_lib.lib().cfd_rbgs3d_zper_ghost())
+    div_p = torch.zeros((c.nz + 2 * G, c.ny, c.nx), device="cuda")
+    div_p[G:G + c.nz].copy_(div)
+    phi_p, tmp_p = torch.zeros_like(div_p), torch.empty_like(div_p)
 
     def run(k):
         mask, levels = legs[k]
         call("cfd_set_jacobi3d_blocking", levels, 0, 0)
+        if k == "p_mask2d_zper":
+            K.solve_pressure_gauss_seidel3d_zper(phi_p, div_p, c.dx, c.dy, c.dz, c.dt, mask, iters, 0.0,
+                                                 workspace=s._gs_ws, iters_done=s._gs_done, phi_tmp=tmp_p, nz=c.nz)
+            return
         K.solve_pressure_gauss_seidel3d(phi, div, c.dx, c.dy, c.dz, c.dt, mask, iters, 0.0, workspace=s._gs_ws,
                                         iters_done=s._gs_done, phi_tmp=tmp)
 
@@ -363,6 +376,68 @@ def cylinder_solves(s, rounds, iters=200):
                       "a2_over_b": round(med["a_mask2d_2_levels"] / med["b_mask3d"], 3),
                       "a_over_c": round(med["a_mask2d"] / med["c_unmasked"], 3), "bar": 0.97,
                       "fused_wins": bool(med[best] < 0.97 * med["b_mask3d"])}), flush=True)
+    print(json.dumps({"bench": "cylinder3d_solve_zper", "periodic_over_free_slip":
+                      round(med["p_mask2d_zper"] / med["a_mask2d"], 3),
+                      "expected_plane_work": round((c.nz + 2 * G) / c.nz, 3), "ghost": G, "bar": 1.15}), flush=True)
+
+
+def cylinder_zper_leg(rounds, launches, steps):
+    """The spanwise-periodic legs next to their free-slip counterparts, each
+    pair alternating window by window: the fused predictor with and without
+    periodic_z on the solver's fields (scalar and LES), then time_step."""
+    from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
+    for les in (False, True):
+        pair = {bc: CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=les, spanwise_bc=bc,
+                                                                    spanwise_perturbation=0.05))
+                for bc in ("free_slip", "periodic")}
+        c = pair["periodic"].config
+        grid, cells = [c.nz, c.ny, c.nx], c.nz * c.ny * c.nx
+        for s in pair.values():
+            for _ in range(2):
+                s.time_step()
+        s = pair["periodic"]
+        o = dict(u_star=s.u_star, v_star=s.v_star, w_star=s.w_star, store_tau=False)
+
+        def pred(per):
+            if les:
+                K.predictor3d_fused_les(s.u, s.v, s.w, c.dx, c.dy, c.dz, DT, c.nu, c.artificial_viscosity,
+                                        c.smagorinsky_constant, c.use_supg, nu_t=s.nu_t, periodic_z=per, **o)
+            else:
+                K.predictor3d_fused(s.u, s.v, s.w, c.dx, c.dy, c.dz, DT, NU, c.use_supg, periodic_z=per, **o)
+
+        ms = {False: [], True: []}
+        for per in ms:
+            for _ in range(3):
+                pred(per)
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for per in ms:
+                ms[per].append(window_ms(lambda: pred(per), launches))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        print(json.dumps({"bench": "cylinder3d_predictor_zper", "grid": grid, "les": les, "path": last_path(),
+                          "ms_free_slip": round(med[False], 4), "ms_periodic": round(med[True], 4),
+                          "ms_min": [round(min(ms[False]), 4), round(min(ms[True]), 4)],
+                          "ms_max": [round(max(ms[False]), 4), round(max(ms[True]), 4)],
+                          "periodic_over_free_slip": round(med[True] / med[False], 3), "rounds": rounds,
+                          "launches_per_round": launches}), flush=True)
+        st = {k: [] for k in pair}
+        for _ in range(rounds):
+            for k, sv in pair.items():
+                st[k].append(window_ms(sv.time_step, steps))
+        med = {k: statistics.median(v) for k, v in st.items()}
+        shape = last_tbr_shape()
+        for k, sv in pair.items():
+            f = sv.force_coefficients()[-1]
+            print(json.dumps({"bench": "cylinder3d_time_step_zper", "grid": grid, "les": les, "spanwise_bc": k,
+                              "pressure": "rbgs", "iterations": c.pressure_iterations, "steps_per_window": steps,
+                              "rounds": rounds, "ms_per_step": round(med[k], 3), "ms_min": round(min(st[k]), 3),
+                              "ms_max": round(max(st[k]), 3), "gcell_per_s": round(cells / med[k] / 1e6, 3),
+                              "w_absmax": float(sv.w.abs().max().item()), "energy_last": sv.energy_history[-1][1],
+                              "cd_last": f[1], "cl_last": f[2]}), flush=True)
+        print(json.dumps({"bench": "cylinder3d_time_step_zper_ratio", "les": les, "last_tbr_shape": shape,
+                          "periodic_over_free_slip": round(med["periodic"] / med["free_slip"], 3)}), flush=True)
+        del pair, s
+        torch.cuda.empty_cache()
 
 
 def cylinder_leg(rounds, launches, steps):
@@ -447,11 +522,15 @@ def main():
     ap.add_argument("--les", action="store_true", help="the LES leg (see above) instead of the scalar-nu one")
     ap.add_argument("--step-only", action="store_true", help="with --les: only the two 512^3 time_step timings")
     ap.add_argument("--cylinder", action="store_true", help="the 3-D cylinder channel leg (see above) and nothing else")
+    ap.add_argument("--zper-only", action="store_true",
+                    help="with --cylinder: only the predictor and time_step pairs of the periodic leg")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_step3d.py needs the GPU")
     if a.cylinder:
-        cylinder_leg(a.rounds, a.launches, 3)
+        if not a.zper_only:
+            cylinder_leg(a.rounds, a.launches, 3)
+        cylinder_zper_leg(a.rounds, a.launches, 3)
         return
     if a.les:
         sizes = [] if a.step_only else [int(s) for s in a.sizes.split(",")]
