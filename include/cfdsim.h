@@ -326,9 +326,28 @@ int cfd_energy_mean_clip2d_f32(float *u, float *v, size_t n, double *out, float 
                                void *stream);
 
 /* ------------------------------------------------------------- reductions */
-/* Each writes one value to a device scalar; the caller zeroes `out` for the
- * max reductions.  Used by the diagnostics (v5.py:410-435), adaptive dt
- * (v5.py:322) and the health monitor (v5.py:599-613). */
+/* Each writes one value to a device scalar.  Used by the diagnostics
+ * (v5.py:410-435), adaptive dt (v5.py:322) and the health monitor
+ * (v5.py:599-613).  The contracts, float32 and float64 alike, which
+ * tests/test_gpu_reductions.py pins:
+ *   maxima (cfd_absmax*, cfd_vorticity_absmax2d_f32, and the absmax / gradmax
+ *     outputs of cfd_divergence2d_*, cfd_project2d_*, cfd_vorticity2d_f64):
+ *     `out` ACCUMULATES -- out = max(out, max|.|) -- so the caller zeroes it
+ *     first, or keeps it to fold several fields into one maximum; a call
+ *     over no cell (n == 0, a grid without an interior) leaves it alone.
+ *     The fold is `if (x > m) m = x` from 0 (v5.py:220-222): a NaN never
+ *     wins, +/-Inf does, -0.0 counts as +0.0, denormals are not flushed.
+ *     `out` must hold a non-negative, non-NaN value.
+ *   count (cfd_nonfinite_count_*): `out` is RESET by the call, then receives
+ *     the number of NaN / +Inf / -Inf entries of a plus those of b (b may be
+ *     NULL).
+ *   means (cfd_mean_*, cfd_energy_mean2d_*, cfd_energy_mean_clip2d_*): `out`
+ *     is OVERWRITTEN (need not be zeroed); float64 partial sums in a fixed
+ *     order, the same bits run to run, up to 2^20 cells; past that the
+ *     energy's partial sums meet in atomics and the last bits may differ from
+ *     run to run (cfd_mean_* keeps its fixed order at any n).  A NaN cell
+ *     makes the mean NaN.  The calls of one stream share one scratch and must
+ *     not run concurrently with each other; each stream has its own. */
 int cfd_absmax_f32(const float *a, size_t n, float *out, void *stream);            /* max|a| */
 int cfd_absmax2_f32(const float *a, const float *b, size_t n, float *out, void *stream);
 int cfd_energy_mean2d_f32(const float *u, const float *v, size_t n, double *out, void *stream);
