@@ -16,6 +16,26 @@
 //             the register queues (z); level K goes to HBM;
 //    barrier.
 //
+// The K = 4 Jacobi pass (LDS-DMA path) differs in two places.  Level 0 is
+// not copied in phase W: its tile is the DMA slot the plane landed in (T0S).
+// And the halo wave issues its global loads after the first barrier, not at
+// the step's start (CFD_TBR_HLD = 2).  Issued at the start, with its phase-W
+// stores behind them in program order, the halo wave reached the first
+// barrier last (per-wave trace: ~2200 cycles into a ~5500-cycle step, the
+// row waves after 700-1350) -- presumably its loads wait for a place in the
+// CU's vector-memory queue behind the row waves' 44 row fetches of the same
+// moment.  Nothing reads the loaded rows before the queues shift at the end
+// of the step, where the halo wave has ~1000 cycles of slack.
+//
+// A variant kept behind CFD_TBR_T1D (off: measured slower) double-buffers
+// T_1 so that the row waves store level 1 in phase R: step z reads level 1
+// of plane z - 1 in buffer (z - zs) & 1 and stores level 1 of plane z into
+// the other one, which was last read in phase R of step z - 1 and is next
+// read in phase R of step z + 1 -- the existing end-of-step barriers (and
+// the phase-W barriers behind them) separate both, no barrier is added.
+// The halo wave keeps storing its level-1 chunks in phase W, into the buffer
+// that step reads.  See DESIGN.md ("K = 4: what bounds phase W").
+//
 // Shapes (K, row waves, rows per wave) -> output rows W = NWR*RPW + 2 - 2K:
 // (3, 11, 2) W = 18; (4, 7, 3) W = 15; (3, 7, 3) W = 17.  Everything else --
 // the halo wave, the z-march bounds, Dirichlet copies, erosion of garbage --
@@ -102,6 +122,15 @@ constexpr int kStoreNt = 2;
 #endif
 #ifndef CFD_TBR_V1  // ROT3: level 0 lives in the slot ring only (see the DMA row wave)
 #define CFD_TBR_V1 1
+#endif
+#ifndef CFD_TBR_HLD  // K = 4 Jacobi halo wave: its global loads at the step's start (0), after its phase-W
+#define CFD_TBR_HLD 2  // stores (1) or after the first barrier (2); see tbr_halo_wave
+#endif
+#ifndef CFD_TBR_T1D  // K = 4 Jacobi: two T_1 buffers, level 1 stored in phase R -- measured slower, off
+#define CFD_TBR_T1D 0  // (see jacobi3d_tbr)
+#endif
+#ifndef CFD_TBR_T1D_LATE  // T1D: that store after the row's level K (1) or right after its level 1 (0)
+#define CFD_TBR_T1D_LATE 1
 #endif
 
 
@@ -417,16 +446,22 @@ __device__ inline v2f_t level2(v2f_t C, v2f_t O, float wl, float er, v2f_t N, v2
 // The halo wave of jacobi3d_tbr (see there): loads the two outermost level-0
 // rows and the 4-float x-halo chunks of every row, and computes levels
 // 1..K-1 of the chunks, in lock step (two barriers per step) with the row waves.
-template <int K, int NWR, int RPW, bool PRE, int PD, int MODE, int F, bool SPLIT, bool PT, bool T0S = false>
+template <int K, int NWR, int RPW, bool PRE, int PD, int MODE, int F, bool SPLIT, bool PT, bool T0S = false,
+          bool T1D = false>
 __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int z0, int z1, int y0, int xs,
-                                              int zl, float *slots = nullptr) {
+                                              int zl, float *slots = nullptr, float *t1b = nullptr) {
     constexpr int NR = NWR * RPW + 2;
     constexpr int RS = 264, RS2 = kPairRow;
     // T0S: level 0 of plane z is slot (z - zs) mod 3 of `slots` (the row
     // waves' LDS-DMA staging ring), the level tiles 1..K-1 start at smem
     int t0 = 0;  // this step's slot offset (floats)
+    // T1D: tile T_1 is the one of its two buffers (smem's, t1b) that this
+    // step's phase R reads, buffer (z - zs) & 1 -- the halo wave stores its
+    // level-1 chunks there in phase W and reads level 1 there in phase R
+    float *t1 = smem;
     auto T = [&](int l, int r) -> float * {
         if (T0S && l == 0) return slots + t0 + r * RS;
+        if (T1D && l == 1) return t1 + (r - 1) * RS;
         int base = 0;
 #pragma unroll
         for (int m = T0S ? 1 : 0; m < K; ++m)
@@ -489,11 +524,21 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
     const int hw = threadIdx.x >> 6;
     for (int z = zs; z <= zl; ++z) {
         if constexpr (T0S) t0 = ((z - zs) % 3) * (NR * RS);
+        if constexpr (T1D) t1 = ((z - zs) & 1) ? t1b : smem;
         trace_mark(a.trace, hw, z - zs, 0);
-        Lq[PD - 1] = ldlo(z + PD);
-        Uq[PD - 1] = ldhi(z + PD);
-        Hq[PD - 1] = ldhp(z + 1 + PD);
-        Rn[PD - 1] = ldh(a.div, z + PD);
+        // the step's global loads (nothing reads them before the queues shift
+        // at the end of the step).  HLD (K = 4 Jacobi, T0S): after the first
+        // barrier, so that the phase-W stores below do not stand behind them
+        // -- 1024^3 A/B against loads at the step's start: 1760 -> 1801
+        // Gcell/s (after the phase-W stores, before the barrier: +0.6 %)
+        constexpr int HLD = T0S && K == 4 ? CFD_TBR_HLD : 0;
+        auto loads = [&] {
+            Lq[PD - 1] = ldlo(z + PD);
+            Uq[PD - 1] = ldhi(z + PD);
+            Hq[PD - 1] = ldhp(z + 1 + PD);
+            Rn[PD - 1] = ldh(a.div, z + PD);
+        };
+        if constexpr (HLD == 0) loads();
         // phase W
         if constexpr (SPLIT) {
             if (elo) sts4s(T(0, 0), lane, lo);
@@ -515,9 +560,11 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
                     }
                 }
         }
+        if constexpr (HLD == 1) loads();
         trace_mark(a.trace, hw, z - zs, 1);
         __syncthreads();
         trace_mark(a.trace, hw, z - zs, 2);
+        if constexpr (HLD == 2) loads();
         // phase R: levels 1..K-1 of the halo chunks
 #pragma unroll
         for (int l = 1; l < K; ++l) {
@@ -626,6 +673,32 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     }();
     __shared__ __attribute__((aligned(16))) float smem[TOTAL > 0 ? TOTAL : 4];
     __shared__ __attribute__((aligned(16))) float slots[T0S ? 3 * SLOT : 4];
+    // T1D (the K = 4 Jacobi at 2 rows per wave on T0S, where LDS has room for
+    // it): a second buffer for T_1, the largest level tile.  Step z (parity
+    // b = (z - zs) & 1, a run-time scalar formed the same way by both wave
+    // kinds) reads level 1 of plane z - 1 from buffer b -- smem's T_1 when
+    // b = 0, t1b when b = 1 -- and the row waves store level 1 of plane z into
+    // buffer 1 - b in phase R (right after computing it, or after the row's
+    // level K: CFD_TBR_T1D_LATE), so phase W has a third fewer ds_write_b128
+    // (22 of 66 per step) in front of its barrier.  No barrier is added: buffer 1 - b was last read in phase R of
+    // step z - 1 (it held plane z - 2) and is next read in phase R of step
+    // z + 1: step z - 1's end-of-step barrier (and step z's phase-W barrier)
+    // lie before this step's stores, step z's end-of-step barrier (and step
+    // z + 1's phase-W barrier) after them.
+    // The halo wave keeps its timing (its level-1 chunks go into buffer b in
+    // phase W of step z, columns the row waves never write).
+    // The phase-R store is not predicated on xin: a branch there splits the
+    // level loop's one basic block (-1 %); a lane beyond nx stores its
+    // never-used value into its own columns, which only such lanes read.
+    // Measured (1024^3, Gcell/s, parent 1766-1771): store right after the
+    // level-1 update 1714 with the predicate, 1730 without; after the row's
+    // level K (CFD_TBR_T1D_LATE) 1735 / 1746.  Phase W was not bound by the
+    // row waves' stores but by the halo wave (see the file header), and the
+    // stores cost phase R more than they saved: off by default.
+    constexpr bool T1D = T0S && K == 4 && RPW == 2 && CFD_TBR_T1D &&
+                         (TOTAL + 3 * SLOT + (NR - 2) * RS) * 4 <= 160 * 1024;
+    constexpr int T1N = (NR - 2) * RS;  // floats of T_1
+    __shared__ __attribute__((aligned(16))) float t1b[T1D ? T1N : 4];
     // DMA staging (row waves, when it fits in LDS with the level tiles): the
     // level-0 row of plane z + 2 and the rhs row of plane z + 1 are fetched by
     // LDS-DMA at the start of step z into the even/odd buffers and read at
@@ -775,6 +848,13 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
         if constexpr (MODE == kRbgs) chgl[slot(l)] = fmaxf(chgl[slot(l)], lm);
     };
 
+    if constexpr (T1D) {
+        // step zs reads buffer 0 before any phase R stored into it: zeros, the
+        // empty level-1 queues' value that phase W used to store there (the
+        // pipeline fill computes from them; nothing of it reaches an output)
+        for (int k = threadIdx.x; k < T1N / 4; k += blockDim.x) sts4(smem + 4 * k, z4);
+        if constexpr (!ZERO) __syncthreads();
+    }
     if constexpr (T0S && ZERO) {
         // level 0 = 0 (no DMA fills the slots): zero them once
         for (int k = threadIdx.x; k < 3 * SLOT / 4; k += blockDim.x) sts4(slots + 4 * k, z4);
@@ -869,6 +949,9 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             // T0S: the lane's float4 in row wv of slot 0, and row wv's first float
             const uint32_t lbS0 = lds_addr(slots) + 4u * (uint32_t)(wv * RS + 4 + 4 * lane);
             const uint32_t lbUS0 = lds_addr(slots) + 4u * (uint32_t)(wv * RS);
+            // T1D: byte distance from T_1's first buffer (smem's) to the second
+            [[maybe_unused]] uint32_t t1dist = 0;
+            if constexpr (T1D) t1dist = lds_addr(t1b) - lds_addr(smem);
             // a row's DMA destination in slot q: row rr[j], column 4
             auto slot_row = [&](int q, int j) { return slots + q * SLOT + rr[j] * RS + 4; };
 #pragma unroll
@@ -1004,13 +1087,28 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 else if constexpr (LB)
                     asm volatile("" : "+v"(bA), "+v"(bU), "+v"(bP));
                 const uint32_t bB = bA + 4u * kTb2, bUB = bU + 4u * kTb2;
+                // T1D: T_1 is read in the buffer of this step's parity (bR1,
+                // bUR1) and level 1 stored into the other (bW1); the second
+                // buffer lies beyond the 16-bit offset of bA, so these are
+                // bases of their own, opaque per step like the others
+                [[maybe_unused]] uint32_t bR1 = 0, bUR1 = 0, bW1 = 0;
+                if constexpr (T1D) {
+                    const bool odd = ((z - zs) & 1) != 0;
+                    const uint32_t t1r = odd ? t1dist : 0u, t1w = odd ? 0u : t1dist;
+                    bR1 = lbA0 + t1r;
+                    bUR1 = lbU0 + t1r;
+                    bW1 = lbA0 + t1w;
+                    asm volatile("" : "+v"(bR1), "+v"(bUR1), "+v"(bW1));
+                }
                 auto tp = [&](int l, int d) -> lfloat * {
                     if (T0S && l == 0) return lds_ptr(bS) + (1 + d) * RS;
+                    if (T1D && l == 1) return lds_ptr(bR1) + (tbase(1) + d * RS);
                     return l < 2 ? lds_ptr(bA) + (tbase(l) + (1 + d - l) * RS)
                                  : lds_ptr(bB) + (tbase(l) - kTb2 + (1 + d - l) * RS);
                 };
                 auto up = [&](int l, int d) -> const lfloat * {
                     if (T0S && l == 0) return lds_ptr(bUS) + (1 + d) * RS;
+                    if (T1D && l == 1) return lds_ptr(bUR1) + (tbase(1) + d * RS);
                     return l < 2 ? lds_ptr(bU) + (tbase(l) + (1 + d - l) * RS)
                                  : lds_ptr(bUB) + (tbase(l) - kTb2 + (1 + d - l) * RS);
                 };
@@ -1063,7 +1161,9 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                     }
 #pragma unroll
                     for (int l = 1; l < K; ++l)
-                        if (xin && rr[j] >= l && rr[j] < NR - l) {
+                        if (T1D && l == 1) {
+                            // (stored in phase R of the step that computed it)
+                        } else if (xin && rr[j] >= l && rr[j] < NR - l) {
                             if constexpr (MODE == kRbgs) {
                                 // level l of plane z - l: its own pair (computed last
                                 // step, at 1 - h) joined with level l - 1's (two steps
@@ -1325,6 +1425,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                     Q[j][l][1] = Q[j][l][2];
                                     Q[j][l][2] = toV(v);
                                 }
+                                // T1D: level 1 of plane z into the T_1 buffer nobody
+                                // reads in this step, for level 2 of the next one
+                                if constexpr (T1D && !CFD_TBR_T1D_LATE) {
+                                    if (l == 1) sts4l(lds_ptr(bW1) + (tbase(1) + j * NWR * RS), v);
+                                }
                             } else {
                                 // unconditional buffer store: rows, lanes and planes this
                                 // tile does not own fall out of range and are dropped
@@ -1345,6 +1450,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                             // join of the two paths cost the hot one a copy of the old
                             // value before the branch and one of the new value after
                             if (l < K) Q[j][l][sl3(R - l + 1)] = toV(any4());
+                        }
+                        if constexpr (T1D && CFD_TBR_T1D_LATE) {  // (every row, also outside level K's range)
+                            if (l == K)
+                                sts4l(lds_ptr(bW1) + (tbase(1) + j * NWR * RS), f4_of(Q[j][1][ROT ? sl3(R) : 2]));
                         }
                         if (EARLY && l == K && !(r >= l && r < NR - l)) {
                             // a row outside level K's range still issues its store
@@ -1533,7 +1642,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
         // K <= 3 one plane (two: neutral for the Jacobi, -2 % for the GS,
         // which then spills a VGPR)
         constexpr int HPD = DMA && K == 4 ? 2 : PD;
-        if constexpr (K == 4)
+        if constexpr (T1D)
+            tbr_halo_wave<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S, true>(a, smem, z0, z1, y0, xs, zl, slots,
+                                                                                t1b);
+        else if constexpr (K == 4)
             tbr_halo_wave<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S>(a, smem, z0, z1, y0, xs, zl, slots);
         else
             tbr_halo_wave_call<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S>(a, smem, z0, z1, y0, xs, zl, slots);

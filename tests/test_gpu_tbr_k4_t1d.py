@@ -1,0 +1,128 @@
+"""The K = 4 Jacobi pass with two level-1 tile buffers (jacobi3d_tbr<4, 11, 2>
+with T1D): bit-identical to K single sweeps (oracle.jacobi3d).
+
+Step z of a z-chunk reads level 1 from buffer (z - zs) & 1 and the row waves
+store the level 1 they compute into the other one during phase R; the halo
+wave stores its x-halo chunks of level 1 into the buffer being read, in phase
+W.  What can go wrong is the parity: between the halo wave and the row waves
+(seen only at the edge between two x-segments, so 264 columns), and at the
+end of a chunk, where the rotated march rounds its step count up to a multiple
+of 3.  Grid (100, 12, 264) with z-chunks of 90..95 planes gives step counts
+96..101 (planes + 6), i.e. both parities of the last step x all three
+round-ups, a partial y-tile, and a clipped last chunk of 10..5 planes that
+runs the shifting-queue instantiation with 16..11 steps (both parities again).
+(40, 31, 520) adds three segments with a partial last one and two y-tiles,
+(11, 40, 16) a single segment; their z-chunks 0, 5, 7 are the whole grid and
+short chunks.  Every first-pass form runs: zero start with a workspace, a
+guess with a workspace, and no workspace; 4, 8 and 9 iterations make a T1D
+pass feed a pass in either ping-pong direction and a remainder pass.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from cfd_simulations_amd import kernels as K
+from cfd_simulations_amd._lib import call
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+H, DT = 0.06, np.float32(3e-3)
+
+CASES = [((100, 12, 264), zc) for zc in (90, 91, 92, 93, 94, 95)] + \
+        [(shape, zc) for shape in ((40, 31, 520), (11, 40, 16)) for zc in (0, 5, 7)]
+ITERS = [4, 8, 9]
+
+
+def dev(a):
+    return torch.tensor(a, device=DEV)  # (a copy: the shared inputs stay read-only)
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def last_shape():
+    v = [ctypes.c_int() for _ in range(4)]
+    call("cfd_get_last_tbr_shape", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+@pytest.fixture(autouse=True)
+def _reset_tuning():
+    call("cfd_reset_tuning")
+    yield
+    call("cfd_reset_tuning")
+
+
+@functools.lru_cache(maxsize=None)
+def fields(shape):
+    rng = np.random.default_rng(47)
+    div = rng.standard_normal(shape).astype(np.float32)
+    phi0 = rng.standard_normal(shape).astype(np.float32)
+    div.setflags(write=False)
+    phi0.setflags(write=False)
+    return div, phi0
+
+
+@functools.lru_cache(maxsize=None)
+def reference(shape, iters, zero):
+    div, phi0 = fields(shape)
+    ref = oracle.jacobi3d(div, h=H, dt=DT, iters=iters) if zero else oracle.jacobi3d(div, phi0, h=H, dt=DT, iters=iters)
+    ref.setflags(write=False)
+    return ref
+
+
+def is_k4(ws, iters):
+    # the last tall-tile launch is a 4-level pass unless the solve ends with a
+    # 2- or 3-level remainder (with the workspace iters % 4 = 1 splits as
+    # 3 + 4 + ... + 2; without it the remainder of 1 is a single sweep)
+    return not ws or iters % 4 == 0
+
+
+def differing(got, ref):
+    n = int(np.count_nonzero(got != ref))
+    return f"{n} of {ref.size} cells differ"
+
+
+@pytest.mark.parametrize("iters", ITERS)
+@pytest.mark.parametrize("shape,zchunk", CASES)
+def test_k4_t1d_guess_bitexact(shape, zchunk, iters):
+    """Solve from a guess without and with the rhs workspace: raw-div passes;
+    the rhs-forming first pass followed by PRE passes."""
+    call("cfd_set_jacobi3d_blocking", 4, 16, zchunk)
+    call("cfd_set_jacobi3d_prefetch", 1)
+    div, phi0 = fields(shape)
+    ref = reference(shape, iters, False)
+    for ws in (False, True):
+        phi = dev(phi0)
+        rhs = torch.empty_like(phi) if ws else None
+        K.solve_pressure_jacobi3d(phi, dev(div), H, DT, None, iters, rhs_ws=rhs)
+        got = host(phi)
+        assert np.array_equal(got, ref), differing(got, ref)
+        if is_k4(ws, iters):
+            assert last_shape()[:3] == (4, 11, 2)
+
+
+@pytest.mark.parametrize("iters", ITERS)
+@pytest.mark.parametrize("shape,zchunk", CASES)
+def test_k4_t1d_zero_start_bitexact(shape, zchunk, iters):
+    """Solve from zeros: with the workspace the first pass is the zero-start,
+    rhs-forming form."""
+    call("cfd_set_jacobi3d_blocking", 4, 16, zchunk)
+    call("cfd_set_jacobi3d_prefetch", 1)
+    div, _ = fields(shape)
+    ref = reference(shape, iters, True)
+    for ws in (False, True):
+        phi = torch.full(shape, 7.0, dtype=torch.float32, device=DEV)  # (the solve starts from zeros itself)
+        rhs = torch.empty_like(phi) if ws else None
+        K.solve_pressure_jacobi3d_zero(phi, dev(div), H, DT, iters, rhs_ws=rhs)
+        got = host(phi)
+        assert np.array_equal(got, ref), differing(got, ref)
+        if is_k4(ws, iters):
+            assert last_shape()[:3] == (4, 11, 2)
