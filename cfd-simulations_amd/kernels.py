@@ -27,6 +27,7 @@ __all__ = [
     "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
     "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
     "apply_channel_bc_ibm3d", "compute_vorticity3d", "solve_pressure_gauss_seidel3d_zper",
+    "accumulate_flow_stats3d",
 ]
 
 
@@ -606,6 +607,24 @@ def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax
          ptr(comp[0]), ptr(comp[1]), ptr(comp[2]), ptr(mag), ptr(absmax), nz, ny, nx, float(dx), float(dy), float(dz),
          stream_handle())
     return (comp[0], comp[1], comp[2], mag) if components else mag
+
+
+def accumulate_flow_stats3d(u, v, w, acc, weight, span_average, nu_t=None):
+    """acc += weight * moments of (nz, ny, nx) float32 u, v, w
+    (cfd_flow_stats3d_f32).  The moments are u, v, w, uu, vv, ww, uv, uw, vw
+    and, with ``nu_t``, nu_t as a tenth, each formed in float64.  ``acc`` is
+    float64: (nm, nz, ny, nx), or with ``span_average`` (nm, ny, nx), which
+    receives weight times the float64 sum over z.  Deterministic (no atomics);
+    every cell counts.  Returns acc."""
+    nz, ny, nx = _fields3d(u, v=v, w=w, nu_t=nu_t)
+    nm = 9 if nu_t is None else 10
+    want = (nm, ny, nx) if span_average else (nm, nz, ny, nx)
+    if acc.dtype != torch.float64 or tuple(acc.shape) != want or acc.device != u.device:
+        raise ValueError(f"acc must be a float64 {want} array on {u.device}, got {tuple(acc.shape)} {acc.dtype} "
+                         f"on {acc.device}")
+    call("cfd_flow_stats3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), ptr(acc), nz, ny, nx, float(weight),
+         1 if span_average else 0, stream_handle())
+    return acc
 
 
 def persistent_failures(stream=None) -> int:

@@ -98,6 +98,39 @@ class OptimizedTurbulentConfig:
             raise ValueError(f"supg_tau must be 'exact' or 'fast', not {self.supg_tau!r}")
 
 
+# ------------------------------------------------------- snapshot files
+# The .npz snapshot files of the 2-D and 3-D solvers: groups step_%06d whose
+# arrays are members "<group>/<name>.npy" of the zip archive.
+def _npz_has_group(path, g):
+    """Whether the snapshot file exists and already holds group ``g``."""
+    import zipfile
+    if not os.path.exists(path):
+        return False
+    with zipfile.ZipFile(path, "r") as z:
+        return f"{g}/u.npy" in z.namelist()
+
+
+def _npz_append(path, groups):
+    """Append the arrays of ``groups`` (member name -> array) to the archive,
+    creating it if need be: a save costs O(one group) however many it holds."""
+    import zipfile
+    with zipfile.ZipFile(path, "a" if os.path.exists(path) else "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for k, arr in groups.items():
+            with z.open(f"{k}.npy", "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arr), allow_pickle=False)
+
+
+def _npz_pick_group(path, f, step):
+    """The name of group ``step`` (None: the latest) of the open file ``f``."""
+    steps = sorted({int(k.split("/")[0][5:]) for k in f.files if k.startswith("step_")})
+    if not steps:
+        raise ValueError(f"{path}: no step_%06d groups")
+    g = f"step_{(steps[-1] if step is None else int(step)):06d}"
+    if f"{g}/u" not in f.files:
+        raise KeyError(f"{path}: no group {g} (have {steps})")
+    return g
+
+
 # ------------------------------------------------------------ host setup
 # One-time host-side setup, kept as pure NumPy functions so the CPU tests can
 # check them against the reference-generated fixtures without a GPU.
@@ -396,23 +429,16 @@ class OptimizedTurbulentSolver:
         device.  phi and the step counter are added (the reference stores
         neither) so that load_snapshot restarts the run exactly; with LES so
         is nu_t (the next adaptive dt reads the previous step's mean nu_t)."""
-        import zipfile
         g = f"step_{step:06d}"
-        exists = os.path.exists(path)
-        if exists:
-            with zipfile.ZipFile(path, "r") as z:
-                if f"{g}/u.npy" in z.namelist():  # `if group_name not in f` (v5.py:458)
-                    return
+        if _npz_has_group(path, g):  # `if group_name not in f` (v5.py:458)
+            return
         groups = {f"{g}/u": self.u.cpu().numpy(), f"{g}/v": self.v.cpu().numpy(),
                   f"{g}/vorticity": self.compute_vorticity().cpu().numpy(),
                   f"{g}/X": self.X, f"{g}/Y": self.Y, f"{g}/phi": self.phi.cpu().numpy(),
                   f"{g}/time": np.float64(current_time), f"{g}/solver_step": np.int64(self.step)}
         if self.config.use_les:
             groups[f"{g}/nu_t"] = self.nu_t.cpu().numpy()
-        with zipfile.ZipFile(path, "a" if exists else "w", compression=zipfile.ZIP_DEFLATED) as z:
-            for k, arr in groups.items():
-                with z.open(f"{k}.npy", "w", force_zip64=True) as f:
-                    np.lib.format.write_array(f, np.asanyarray(arr), allow_pickle=False)
+        _npz_append(path, groups)
 
     def load_snapshot(self, path, step=None):
         """Restart from a save_snapshot file: group step_%06d (the latest
@@ -421,12 +447,7 @@ class OptimizedTurbulentSolver:
         run's bit for bit: a step reads only u, v and the counter (phi is
         zero-filled before each solve, v5.py:331/337)."""
         with np.load(path, allow_pickle=False) as f:
-            steps = sorted({int(k.split("/")[0][5:]) for k in f.files if k.startswith("step_")})
-            if not steps:
-                raise ValueError(f"{path}: no step_%06d groups")
-            g = f"step_{(steps[-1] if step is None else int(step)):06d}"
-            if f"{g}/u" not in f.files:
-                raise KeyError(f"{path}: no group {g} (have {steps})")
+            g = _npz_pick_group(path, f, step)
             shape = (self.config.ny, self.config.nx)
             if f[f"{g}/u"].shape != shape:
                 raise ValueError(f"{path}: {g} holds a {f[f'{g}/u'].shape} grid, the solver {shape}")
@@ -549,6 +570,24 @@ class LesCavity3DConfig(LidDrivenCavity3DConfig):
     _accepts_les = True
 
 
+STATS_MOMENTS = ("u", "v", "w", "uu", "vv", "ww", "uv", "uw", "vw", "nu_t")
+
+
+def derive_statistics(sums, weight, nz, span_average):
+    """The averages of the float64 moment sums (STATS_MOMENTS' order; 9 or 10
+    planes): every sum over weight * nz (span_average) or weight, the Reynolds
+    stresses <ab> - <a><b>, tke = ((uu + vv) + ww) / 2."""
+    norm = np.float64(weight) * np.float64(nz) if span_average else np.float64(weight)
+    m = np.asarray(sums, np.float64) / norm
+    out = {"weight": float(weight), "mean_u": m[0], "mean_v": m[1], "mean_w": m[2]}
+    for q, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+        out[STATS_MOMENTS[3 + q]] = m[3 + q] - m[a] * m[b]
+    out["tke"] = 0.5 * ((out["uu"] + out["vv"]) + out["ww"])
+    if m.shape[0] == 10:
+        out["mean_nu_t"] = m[9]
+    return out
+
+
 class LidDrivenCavity3DSolver:
     """The projection step around the 3-D pressure solves on one GPU: the
     project's own 3-D generalisation of the v5 time step (every 2-D
@@ -567,12 +606,27 @@ class LidDrivenCavity3DSolver:
     dt reads the float64 mean of the previous step's nu_t together with
     max|V| in the same single host read.
 
-    Out of scope: snapshots, immersed boundaries or masks (those:
+    Statistics (``enable_statistics``): float64 running sums of u, v, w, uu,
+    vv, ww, uv, uw, vw (and nu_t with LES) of the step's final, clipped
+    fields, one K.accumulate_flow_stats3d launch per sampled step, per cell or
+    summed over z; ``statistics()`` derives the means, the Reynolds stresses
+    and the turbulent kinetic energy.  With statistics off time_step launches
+    what it launched without them.
+
+    Snapshots: ``save_snapshot`` / ``load_snapshot`` keep the 2-D solver's
+    .npz layout (groups step_%06d, appended) with u, v, w, phi, |omega|, the
+    axes, nu_t with LES and the statistics' sums and settings; after a load
+    every later step, field and statistics sum equals the uninterrupted run's
+    bit for bit.
+
+    Out of scope: immersed boundaries or masks (those:
     CylinderChannel3DSolver), float64, a
     slab-decomposed (multi-GPU) step, and the 2-D step's clean_divergence
     stage (a v5 quirk with serial semantics that does not generalise)."""
 
     _periodic_z = False  # CylinderChannel3DSolver with spanwise_bc="periodic": the *_zper stages
+    _stats_span_default = False  # enable_statistics(span_average=None); the cylinder channel: True
+    _stats = None  # (start_step, interval, span_average, weight) once statistics are enabled
 
     def __init__(self, config: LidDrivenCavity3DConfig):
         self.config = cfg = config
@@ -712,8 +766,173 @@ class LidDrivenCavity3DSolver:
              ptr(self._energy_slot()), -float(cfg.max_velocity), float(cfg.max_velocity), stream_handle())
         self._energy_steps.append(self.step)
         self.times.append(self.step * dt)
+        if self._stats is not None:
+            self._sample_statistics(dt)
         self.step += 1
         return dt
+
+    # -------------------------------------------------------- statistics
+    def enable_statistics(self, start_step=0, interval=1, span_average=None, weight="dt"):
+        """Accumulate the flow moments of the clipped u, v, w (with LES also
+        nu_t) at the end of every step k >= start_step with (k - start_step) %
+        interval == 0, into zeroed float64 sums on the device.
+        ``span_average`` (None: True for the cylinder channel, False for the
+        cavity): sum over z into (ny, nx) planes instead of keeping
+        (nz, ny, nx).  ``weight``: "dt" weights a sample by its step's dt
+        (the dt is adaptive from step 1000 on, so equal weights would bias a
+        time average), "sample" by 1.0.  Calling it again with the same
+        settings does nothing; other settings raise ValueError unless
+        reset_statistics() came first."""
+        if span_average is None:
+            span_average = self._stats_span_default
+        if weight not in ("dt", "sample"):
+            raise ValueError(f"enable_statistics: weight must be 'dt' or 'sample', not {weight!r}")
+        if int(start_step) < 0 or int(interval) < 1:
+            raise ValueError(f"enable_statistics: start_step >= 0 and interval >= 1 (got {start_step}, {interval})")
+        settings = (int(start_step), int(interval), bool(span_average), weight)
+        if self._stats is not None:
+            if settings == self._stats:
+                return
+            if not self._stats_reset:
+                raise ValueError(f"enable_statistics: statistics are on with {self._stats}, asked for {settings}; "
+                                 "call reset_statistics() first")
+        cfg = self.config
+        nm = 10 if self.use_les else 9
+        shape = (nm, cfg.ny, cfg.nx) if settings[2] else (nm, cfg.nz, cfg.ny, cfg.nx)
+        self._stats = settings
+        self._stats_sums = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        self._stats_weight = np.float64(0.0)
+        self._stats_samples = 0
+        self._stats_reset = False
+
+    def reset_statistics(self):
+        """Zero the sums, the total weight and the sample count; the settings
+        stay."""
+        if self._stats is None:
+            raise RuntimeError("reset_statistics: statistics are not enabled")
+        self._stats_sums.zero_()
+        self._stats_weight = np.float64(0.0)
+        self._stats_samples = 0
+        self._stats_reset = True
+
+    def _sample_statistics(self, dt):
+        start, interval, span, mode = self._stats
+        k = self.step
+        if k < start or (k - start) % interval:
+            return
+        wgt = float(dt) if mode == "dt" else 1.0
+        K.accumulate_flow_stats3d(self.u, self.v, self.w, self._stats_sums, wgt, span,
+                                  nu_t=self.nu_t if self.use_les else None)
+        self._stats_weight = self._stats_weight + np.float64(wgt)
+        self._stats_samples += 1
+        self._stats_reset = False
+
+    def statistics(self):
+        """The averages so far, float64 NumPy arrays from one device read:
+        ``samples``, ``weight`` (the total), ``mean_u``, ``mean_v``,
+        ``mean_w``, the Reynolds stresses ``uu``, ``vv``, ``ww``, ``uv``,
+        ``uw``, ``vw`` as <ab> - <a><b>, ``tke`` = (uu + vv + ww) / 2 and,
+        with LES, ``mean_nu_t``.  Shapes: (ny, nx) with span_average (the sums
+        over weight * nz), else (nz, ny, nx) (over weight).  RuntimeError
+        before the first sample."""
+        if self._stats is None or self._stats_samples == 0:
+            raise RuntimeError("statistics(): no sample yet (enable_statistics, then time_step)")
+        sums = self._stats_sums.cpu().numpy()  # the one device read
+        out = derive_statistics(sums, self._stats_weight, self.config.nz, self._stats[2])
+        out["samples"] = self._stats_samples
+        return out
+
+    # ----------------------------------------------------------- output
+    def compute_vorticity(self):
+        """|omega| of the current fields, 0 on the six faces."""
+        cfg = self.config
+        return K.compute_vorticity3d(self.u, self.v, self.w, cfg.dx, cfg.dy, cfg.dz)
+
+    def save_snapshot(self, path, step: int, current_time: float):
+        """The 2-D solver's snapshot file in 3-D: group step_%06d of the .npz
+        archive with u, v, w, phi, vorticity (|omega| from compute_vorticity),
+        the axes x, y, z, time, solver_step, nu_t with LES and, when
+        statistics are enabled, stats_sums, stats_weight, stats_samples and
+        the four settings (stats_start_step, stats_interval,
+        stats_span_average, stats_weight_mode).  An existing file keeps its
+        groups and gains this one as appended zip members; a group already
+        present is left alone without reading the device."""
+        g = f"step_{step:06d}"
+        if _npz_has_group(path, g):
+            return
+        cfg = self.config
+        z = getattr(self, "z", None)
+        host = lambda t: t.cpu().numpy()  # noqa: E731
+        groups = {f"{g}/u": host(self.u), f"{g}/v": host(self.v), f"{g}/w": host(self.w),
+                  f"{g}/phi": host(self.phi), f"{g}/vorticity": host(self.compute_vorticity()),
+                  f"{g}/x": np.linspace(cfg.x_min, cfg.x_max, cfg.nx),
+                  f"{g}/y": np.linspace(cfg.y_min, cfg.y_max, cfg.ny),
+                  f"{g}/z": np.linspace(cfg.z_min, cfg.z_max, cfg.nz) if z is None else z,
+                  f"{g}/time": np.float64(current_time), f"{g}/solver_step": np.int64(self.step)}
+        if self.use_les:
+            groups[f"{g}/nu_t"] = host(self.nu_t)
+        if self._stats is not None:
+            start, interval, span, mode = self._stats
+            groups.update({f"{g}/stats_sums": host(self._stats_sums),
+                           f"{g}/stats_weight": np.float64(self._stats_weight),
+                           f"{g}/stats_samples": np.int64(self._stats_samples),
+                           f"{g}/stats_start_step": np.int64(start), f"{g}/stats_interval": np.int64(interval),
+                           f"{g}/stats_span_average": np.bool_(span), f"{g}/stats_weight_mode": np.array(mode)})
+        _npz_append(path, groups)
+
+    def load_snapshot(self, path, step=None):
+        """Restart from a save_snapshot file: group step_%06d (the latest
+        when ``step`` is None) gives u, v, w, phi, nu_t (LES), the step counter
+        and, if the group holds them, the statistics: they are enabled with
+        the stored settings if they are off, and a solver whose statistics are
+        on with other settings raises ValueError, as does a file of another
+        grid shape.  Returns the stored time.  The histories (energy, forces)
+        start empty, on a solver that has already stepped too.  Two cases are
+        accepted and fall outside the guarantee below: a group without nu_t
+        (written with LES off) leaves an LES solver's nu_t as it is, which
+        the adaptive dt reads from step 1000 on; a group without statistics
+        (written with them off) leaves the solver's running sums, weight and
+        count as they are, so averaging can start from a spin-up file.
+        Otherwise every later time_step(), field and statistics sum then
+        equals the uninterrupted run's bit for bit: a step reads only u, v, w,
+        the counter and, with LES from step 1000 on, the mean of nu_t, and the
+        statistics kernel's sums have a fixed order."""
+        cfg = self.config
+        with np.load(path, allow_pickle=False) as f:
+            g = _npz_pick_group(path, f, step)
+            shape = (cfg.nz, cfg.ny, cfg.nx)
+            if f[f"{g}/u"].shape != shape:
+                raise ValueError(f"{path}: {g} holds a {f[f'{g}/u'].shape} grid, the solver {shape}")
+            has_stats = f"{g}/stats_sums" in f.files
+            if has_stats:
+                settings = (int(f[f"{g}/stats_start_step"]), int(f[f"{g}/stats_interval"]),
+                            bool(f[f"{g}/stats_span_average"]), str(f[f"{g}/stats_weight_mode"]))
+                if self._stats is not None and self._stats != settings:
+                    raise ValueError(f"{path}: {g} holds statistics with {settings}, the solver's are on with "
+                                     f"{self._stats}")
+                sums = f[f"{g}/stats_sums"]
+                nm = 10 if self.use_les else 9
+                want = (nm, cfg.ny, cfg.nx) if settings[2] else (nm, *shape)
+                if sums.shape != want:
+                    raise ValueError(f"{path}: {g} holds {sums.shape} statistics sums, the solver {want}")
+            for name in ("u", "v", "w", "phi"):  # phi may be a view of the padded array: copy into it
+                getattr(self, name).copy_(torch.from_numpy(f[f"{g}/{name}"]))
+            if self.use_les and f"{g}/nu_t" in f.files:
+                self.nu_t.copy_(torch.from_numpy(f[f"{g}/nu_t"]))
+            if has_stats:
+                if self._stats is None:
+                    self.enable_statistics(*settings)
+                self._stats_sums.copy_(torch.from_numpy(sums))
+                self._stats_weight = np.float64(f[f"{g}/stats_weight"])
+                self._stats_samples = int(f[f"{g}/stats_samples"])
+                self._stats_reset = False
+            self.step = int(f[f"{g}/solver_step"])
+            self._restart_histories()
+            return float(f[f"{g}/time"])
+
+    def _restart_histories(self):
+        self._energy_steps = []
+        self.times = []
 
 
 # ------------------------------------------------- 3-D cylinder channel
@@ -809,9 +1028,17 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     spanwise_perturbation (either spanwise_bc) scales the initial u per plane,
     which is what makes a run three-dimensional.
 
+    Statistics and snapshots are the cavity solver's (enable_statistics,
+    statistics, save_snapshot, load_snapshot); here the statistics default to
+    the span average, the mean flow and Reynolds stresses over time and z on
+    the (ny, nx) plane, and a snapshot's vorticity is NaN in the cylinder.
+
     Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
     single sweeps: DESIGN.md 4.4), a periodic form of that Jacobi, masks that
-    vary along z in the fused GS, snapshots, float64 and the slab path."""
+    vary along z in the fused GS, pressure statistics (the step keeps no p), a
+    Strouhal estimate from the lift history, float64 and the slab path."""
+
+    _stats_span_default = True
 
     def __init__(self, config: CylinderChannel3DConfig):
         super().__init__(config)
@@ -900,6 +1127,11 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         dt = super().time_step()
         self._dts.append(float(dt))
         return dt
+
+    def _restart_histories(self):
+        super()._restart_histories()
+        self._dts = []
+        self._force.zero_()  # the forcing kernel adds into its step's row, and the rows are handed out from 0 again
 
     def compute_vorticity(self):
         """|omega| of the current fields: 0 on the six faces (periodic: the

@@ -578,6 +578,24 @@ int cfd_vorticity3d_f32(const float *u, const float *v, const float *w, const ui
 int cfd_vorticity3d_zper_f32(const float *u, const float *v, const float *w, const uint8_t *mask,
                              float *ox, float *oy, float *oz, float *mag, float *absmax,
                              int nz, int ny, int nx, double dx, double dy, double dz, void *stream);
+/* Running sums for the mean flow and the Reynolds stresses of (nz, ny, nx)
+ * float32 u, v, w.  The moments of a cell are, in this order, u, v, w, uu, vv,
+ * ww, uv, uw, vw, and nu_t as a tenth when nu_t is given (nm = 9 or 10); each
+ * is formed in double from the float32 values loaded (a product is exact).
+ *   span_average = 0: acc is (nm, nz, ny, nx) float64,
+ *                     acc[m, k, i, j] += weight * t_m(k, i, j);
+ *   span_average = 1: acc is (nm, ny, nx) float64,
+ *                     acc[m, i, j] += weight * sum_k t_m(k, i, j), the z sum
+ *                     formed in float64, multiplied by weight once and added
+ *                     to acc once.
+ * Every cell counts (no mask; NaN propagates).  No atomics, no allocation and
+ * no workspace: the order of a column's z sum depends on the shape alone
+ * (eight contiguous chunks of ceil(nz / 8) planes, each summed in plane order,
+ * the chunk sums added in order), so the result has the same bits run to run.
+ * Any nx and ny >= 1, nz >= 1.  u, v, w must be three arrays; weight finite. */
+int cfd_flow_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t,
+                         double *acc, int nz, int ny, int nx, double weight, int span_average,
+                         void *stream);
 
 /* --------------------------------------------------- float64 fields */
 /* memory_efficient=False (v5.py:287-296): every field float64; the kernels

@@ -41,6 +41,15 @@ periodic leg: the fused predictor with and without periodic_z on the same
 fields (scalar and LES) and time_step with spanwise_bc "free_slip" and
 "periodic", each pair alternating window by window (medians of the rounds).
 
+--stats: the flow statistics leg instead, at the same grid:
+cfd_flow_stats3d_f32 in span mode without and with nu_t and in full mode (one
+moment plane per column, or per cell), and cfd_vorticity3d_f32 writing |omega|
+only as the yardstick of the same session, alternating window by window, each
+with its algorithmic bytes (the fields read once, 16 B per accumulator
+element), the time those bytes take at the HBM peak and the fraction of the
+peak reached; then CylinderChannel3DSolver.time_step with statistics off, in
+span mode and in full mode, the three solvers alternating window by window.
+
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
 `--les --sizes 512 --no-step`, `--les --sizes 1024 --no-step --check`, then
@@ -510,6 +519,84 @@ def cylinder_leg(rounds, launches, steps):
         torch.cuda.empty_cache()
 
 
+def stats_leg(rounds, launches, steps, step_only=False):
+    """The flow statistics at the default 600 x 180 x 120 grid:
+    cfd_flow_stats3d_f32 in span mode without and with nu_t and in full mode,
+    with cfd_vorticity3d_f32 (|omega| only, masked) as the yardstick, the legs
+    alternating window by window; then CylinderChannel3DSolver.time_step with
+    statistics off, in span mode and in full mode, the solvers alternating."""
+    from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
+    c = CylinderChannel3DConfig()
+    nz, ny, nx = c.nz, c.ny, c.nx
+    cells, cols = nz * ny * nx, ny * nx
+    grid = [nz, ny, nx]
+    if not step_only:
+        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=True, spanwise_perturbation=0.05))
+        for _ in range(2):
+            s.time_step()   # fields that depend on z, and a nu_t
+        mag = torch.empty_like(s.u)
+        span9, span10 = (torch.zeros((nm, ny, nx), dtype=torch.float64, device="cuda") for nm in (9, 10))
+        full9 = torch.zeros((9, nz, ny, nx), dtype=torch.float64, device="cuda")
+
+        def vort():
+            call("cfd_vorticity3d_f32", _lib.ptr(s.u), _lib.ptr(s.v), _lib.ptr(s.w), _lib.ptr(s.cylinder_mask), None,
+                 None, None, _lib.ptr(mag), None, nz, ny, nx, c.dx, c.dy, c.dz, _lib.stream_handle())
+
+        # algorithmic bytes: the fields read once; an accumulator element read and written once
+        cases = {"stats_span": (lambda: K.accumulate_flow_stats3d(s.u, s.v, s.w, span9, 2e-5, True),
+                                12 * cells + 16 * 9 * cols),
+                 "stats_span_nu_t": (lambda: K.accumulate_flow_stats3d(s.u, s.v, s.w, span10, 2e-5, True,
+                                                                       nu_t=s.nu_t), 16 * cells + 16 * 10 * cols),
+                 "stats_full": (lambda: K.accumulate_flow_stats3d(s.u, s.v, s.w, full9, 2e-5, False),
+                                (12 + 16 * 9) * cells),
+                 "vorticity3d": (vort, 17 * cells)}      # u, v, w and the mask read, |omega| written
+        ms = {k: [] for k in cases}
+        for fn, _ in cases.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for k, (fn, _) in cases.items():
+                ms[k].append(window_ms(fn, launches))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, v in ms.items():
+            nbytes = cases[k][1]
+            print(json.dumps({"bench": "stats3d_kernel", "grid": grid, "kernel": k, "ms": round(med[k], 4),
+                              "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                              "windows_ms": [round(x, 4) for x in v], "rounds": rounds,
+                              "launches_per_round": launches, "algorithmic_bytes": nbytes,
+                              "ms_at_hbm_peak": round(nbytes / HBM_PEAK * 1e3, 4),
+                              "hbm_fraction": round(nbytes / (med[k] * 1e-3) / HBM_PEAK, 4)}), flush=True)
+        spread = max(max(v) - min(v) for v in (ms["stats_span"], ms["vorticity3d"]))
+        print(json.dumps({"bench": "stats3d_span_vs_vorticity", "span_over_vorticity":
+                          round(med["stats_span"] / med["vorticity3d"], 3), "window_spread_ms": round(spread, 4),
+                          "span_not_slower": bool(med["stats_span"] <= med["vorticity3d"] + spread)}), flush=True)
+        del s, mag, span9, span10, full9, cases
+        torch.cuda.empty_cache()
+    modes = {"off": None, "span": True, "full": False}
+    solvers = {}
+    for k, span in modes.items():
+        sv = solvers[k] = CylinderChannel3DSolver(CylinderChannel3DConfig(spanwise_perturbation=0.05))
+        if span is not None:
+            sv.enable_statistics(span_average=span)
+        for _ in range(2):
+            sv.time_step()
+    torch.cuda.synchronize()
+    st = {k: [] for k in solvers}
+    for _ in range(rounds):
+        for k, sv in solvers.items():
+            st[k].append(window_ms(sv.time_step, steps))
+    med = {k: statistics.median(v) for k, v in st.items()}
+    for k, sv in solvers.items():
+        print(json.dumps({"bench": "stats3d_time_step", "grid": grid, "statistics": k, "les": False,
+                          "pressure": "rbgs", "iterations": c.pressure_iterations, "steps_per_window": steps,
+                          "rounds": rounds, "ms_per_step": round(med[k], 3), "ms_min": round(min(st[k]), 3),
+                          "ms_max": round(max(st[k]), 3), "windows_ms": [round(x, 3) for x in st[k]],
+                          "delta_ms_over_off": round(med[k] - med["off"], 3),
+                          "samples": 0 if k == "off" else sv.statistics()["samples"],
+                          "energy_last": sv.energy_history[-1][1]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="512,1024")
@@ -524,9 +611,14 @@ def main():
     ap.add_argument("--cylinder", action="store_true", help="the 3-D cylinder channel leg (see above) and nothing else")
     ap.add_argument("--zper-only", action="store_true",
                     help="with --cylinder: only the predictor and time_step pairs of the periodic leg")
+    ap.add_argument("--stats", action="store_true", help="the flow statistics leg (see above) and nothing else")
+    ap.add_argument("--stats-step-only", action="store_true", help="with --stats: only the three time_step timings")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_step3d.py needs the GPU")
+    if a.stats:
+        stats_leg(a.rounds, a.launches, 3, a.stats_step_only)
+        return
     if a.cylinder:
         if not a.zper_only:
             cylinder_leg(a.rounds, a.launches, 3)
