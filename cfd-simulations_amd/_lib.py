@@ -115,6 +115,16 @@ PROTOTYPES = {
                                                c_double, c_int, c_int, c_int, c_int, P, P]),
     "cfd_apply_channel_bc_ibm3d_zper_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_int,
                                                     c_double, c_int, c_int, c_int, c_int, P, P]),
+    "cfd_scalar_advance3d_f32": (c_int, [P, P, P, P, c_float, P, c_float, P, c_int, c_int, c_int, c_double, c_double,
+                                         c_double, c_float, c_int, P]),
+    "cfd_scalar_advance3d_zper_f32": (c_int, [P, P, P, P, c_float, P, c_float, P, c_int, c_int, c_int, c_double,
+                                              c_double, c_double, c_float, c_int, P]),
+    "cfd_set_scalar3d_config": (c_int, [c_int, c_int, c_int, c_int]),
+    "cfd_get_last_scalar3d_path": (c_int, [ctypes.POINTER(c_int)]),
+    "cfd_scalar_bc_heat3d_f32": (c_int, [P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_int,
+                                         c_int, c_int, P, P]),
+    "cfd_scalar_bc_heat3d_zper_f32": (c_int, [P, P, c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_int,
+                                              c_int, c_int, P, P]),
     "cfd_vorticity3d_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double,
                                     P]),
     "cfd_vorticity3d_zper_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double,

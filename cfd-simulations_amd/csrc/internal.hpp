@@ -70,6 +70,10 @@ struct Tuning {
     // cells per lane (0: 4, 2 below 256 columns; 1, 2, 4), halved until nx
     // and every pointer's alignment fit
     int pred3_variant = 0, pred3_rows = 0, pred3_vec = 0;
+    // passive scalar advance (cfd_scalar_advance3d_f32): the same three knobs
+    // with the same meaning (cells per lane 0: 2), and the march's planes per
+    // chunk (0: auto)
+    int scal3_variant = 0, scal3_rows = 0, scal3_vec = 0, scal3_zchunk = 0;
     // persistent small-grid solves (jacobi2d_persist, rbgs2d_persist): 0 = a
     // plain launch after the occupancy check (r05 default: the cooperative
     // launch cost ~30 us of queue gap per solve, 0.79 -> 0.76 ms per v5

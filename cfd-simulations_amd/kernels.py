@@ -27,7 +27,7 @@ __all__ = [
     "predictor3d_fused", "compute_divergence3d", "project_velocity3d", "apply_lid_bc3d",
     "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
     "apply_channel_bc_ibm3d", "compute_vorticity3d", "solve_pressure_gauss_seidel3d_zper",
-    "accumulate_flow_stats3d",
+    "accumulate_flow_stats3d", "scalar_advance3d", "apply_scalar_bc_heat3d",
 ]
 
 
@@ -587,6 +587,52 @@ def apply_channel_bc_ibm3d(u, v, w, y, ibm_mask2d, y_max, v_inf, step, force_str
          ptr(w), ptr(y), ptr(ibm_mask2d), nz, ny, nx, float(y_max), float(v_inf), int(step), float(force_strength),
          i0, i1, j0, j1, ptr(force_out), stream_handle())
     return u, v, w
+
+
+def scalar_advance3d(T, u, v, w, alpha, dt, dx, dy, dz, use_supg=True, *, nu_t=None, inv_prt=0.0, out,
+                     periodic_z=False):
+    """The passive scalar's advance (cfd_scalar_advance3d_f32), one launch:
+    out = T + dt*(-conv + lap) on the interior with the 3-D predictor's
+    per-field arithmetic applied to T, advected by the cell's own u, v, w, the
+    diffusivity ``alpha`` (a scalar, rounded to float32) in place of nu -- or,
+    with ``nu_t`` (an array of the fields' shape), alpha + nu_t * inv_prt per
+    cell in float32 (``inv_prt``: float32(1 / turbulent Prandtl number)).  The
+    six faces copy T through.  ``out`` must be given and be none of the
+    inputs.  ``periodic_z``: every plane is interior in z and z wraps
+    (cfd_scalar_advance3d_zper_f32).  Returns out."""
+    nz, ny, nx = _fields3d(T, u=u, v=v, w=w, nu_t=nu_t, out=out)
+    call("cfd_scalar_advance3d_zper_f32" if periodic_z else "cfd_scalar_advance3d_f32", ptr(T), ptr(u), ptr(v),
+         ptr(w), float(np.float32(alpha)), ptr(nu_t), float(np.float32(inv_prt)), ptr(out), nz, ny, nx, float(dx),
+         float(dy), float(dz), _dt_arg(dt, T.dtype), int(bool(use_supg)), stream_handle())
+    return out
+
+
+def apply_scalar_bc_heat3d(T, ibm_mask2d, t_in, t_cyl, force_strength, *, bbox=None, heat_out=None,
+                           periodic_z=False):
+    """Heating by the immersed boundary, then the scalar's faces, in place on
+    the (nz, ny, nx) float32 ``T`` (cfd_scalar_bc_heat3d_f32): every non-face
+    cell where the float64 (ny, nx) ``ibm_mask2d`` (None: no heating) is
+    positive relaxes towards ``t_cyl``, T += (m * force_strength)(t_cyl - T)
+    formed in float64 and rounded once; then the spanwise faces, the adiabatic
+    channel walls and the outlet copy their interior neighbour and the inlet
+    column is ``t_in``.  ``bbox`` = (i0, i1, j0, j1): half-open rows and
+    columns holding every m > 0 (None: the whole plane); only that box is
+    visited for the heating.  ``heat_out``: optional float64 device tensor of
+    one element, added to: the sum of after - before over the heated cells.
+    ``periodic_z``: no spanwise faces (cfd_scalar_bc_heat3d_zper_f32).
+    Returns T."""
+    nz, ny, nx = _fields3d(T)
+    if ibm_mask2d is not None and (ibm_mask2d.dtype != torch.float64 or tuple(ibm_mask2d.shape) != (ny, nx)
+                                   or ibm_mask2d.device != T.device):
+        raise ValueError(f"ibm_mask2d must be a float64 ({ny}, {nx}) array on {T.device}, got "
+                         f"{tuple(ibm_mask2d.shape)} {ibm_mask2d.dtype} on {ibm_mask2d.device}")
+    if heat_out is not None and (heat_out.dtype != torch.float64 or heat_out.numel() != 1
+                                 or heat_out.device != T.device):
+        raise ValueError("heat_out must be one float64 element on the field's device")
+    i0, i1, j0, j1 = (0, ny, 0, nx) if bbox is None else (int(b) for b in bbox)
+    call("cfd_scalar_bc_heat3d_zper_f32" if periodic_z else "cfd_scalar_bc_heat3d_f32", ptr(T), ptr(ibm_mask2d), nz,
+         ny, nx, float(t_in), float(t_cyl), float(force_strength), i0, i1, j0, j1, ptr(heat_out), stream_handle())
+    return T
 
 
 def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax=None, periodic_z=False):

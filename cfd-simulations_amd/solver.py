@@ -709,6 +709,10 @@ class LidDrivenCavity3DSolver:
     def apply_boundary_conditions(self, u, v, w):
         K.apply_lid_bc3d(u, v, w, self.config.lid_velocity)
 
+    def _after_predictor(self, dt):
+        """Stages that read the step's incoming u, v, w (and nu_t) before the
+        projection overwrites them: none here (the cylinder channel's scalar)."""
+
     @property
     def energy_history(self):
         """[(step, mean kinetic energy)], read lazily from the device."""
@@ -754,6 +758,7 @@ class LidDrivenCavity3DSolver:
             K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
                                 v_star=self.v_star, w_star=self.w_star, store_tau=False,
                                 periodic_z=self._periodic_z)
+        self._after_predictor(dt)
         self.apply_boundary_conditions(self.u_star, self.v_star, self.w_star)
         K.compute_divergence3d(self.u_star, self.v_star, self.w_star, *sp, out=self.div_u_star,
                                absmax=self._scal[1:2] if diag else None, periodic_z=self._periodic_z)
@@ -878,7 +883,13 @@ class LidDrivenCavity3DSolver:
                            f"{g}/stats_samples": np.int64(self._stats_samples),
                            f"{g}/stats_start_step": np.int64(start), f"{g}/stats_interval": np.int64(interval),
                            f"{g}/stats_span_average": np.bool_(span), f"{g}/stats_weight_mode": np.array(mode)})
+        groups.update({f"{g}/{name}": host(t) for name, t in self._snapshot_fields().items()})
         _npz_append(path, groups)
+
+    def _snapshot_fields(self):
+        """Further device fields of a snapshot group, {name: tensor}, restored
+        by load_snapshot when the group holds them (the cylinder channel: T)."""
+        return {}
 
     def load_snapshot(self, path, step=None):
         """Restart from a save_snapshot file: group step_%06d (the latest
@@ -919,6 +930,9 @@ class LidDrivenCavity3DSolver:
                 getattr(self, name).copy_(torch.from_numpy(f[f"{g}/{name}"]))
             if self.use_les and f"{g}/nu_t" in f.files:
                 self.nu_t.copy_(torch.from_numpy(f[f"{g}/nu_t"]))
+            for name, t in self._snapshot_fields().items():
+                if f"{g}/{name}" in f.files:
+                    t.copy_(torch.from_numpy(f[f"{g}/{name}"]))
             if has_stats:
                 if self._stats is None:
                     self.enable_statistics(*settings)
@@ -962,9 +976,21 @@ class CylinderChannel3DConfig(OptimizedTurbulentConfig):
     hdf5_file: str = "cylinder3d_re_600.h5"
     spanwise_bc: str = "free_slip"
     spanwise_perturbation: float = 0.0
+    # passive scalar (temperature): off by default.  Diffusivity nu / prandtl
+    # (artificial_viscosity is not added), with LES plus nu_t /
+    # turbulent_prandtl per cell; T = scalar_inlet at the inlet and at the
+    # start, the cylinder's forcing zone relaxes T towards scalar_cylinder
+    scalar: bool = False
+    prandtl: float = 0.71
+    turbulent_prandtl: float = 0.85
+    scalar_inlet: float = 0.0
+    scalar_cylinder: float = 1.0
 
     def __post_init__(self):
         super().__post_init__()
+        if not (self.prandtl > 0.0 and self.turbulent_prandtl > 0.0):
+            raise ValueError(f"CylinderChannel3DConfig: prandtl and turbulent_prandtl must be positive "
+                             f"(got {self.prandtl}, {self.turbulent_prandtl})")
         if self.spanwise_bc not in ("free_slip", "periodic"):
             raise ValueError(f"CylinderChannel3DConfig: spanwise_bc must be 'free_slip' or 'periodic', "
                              f"not {self.spanwise_bc!r}")
@@ -1033,10 +1059,24 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     the span average, the mean flow and Reynolds stresses over time and z on
     the (ny, nx) plane, and a snapshot's vorticity is NaN in the cylinder.
 
+    Passive scalar (config.scalar=True; off by default, and then nothing is
+    allocated or launched): ``T`` starts at scalar_inlet.  Each step, directly
+    after the predictor, K.scalar_advance3d advances it with the step's
+    incoming u, v, w (diffusivity f32(nu / prandtl), with LES plus nu_t /
+    turbulent_prandtl per cell from the nu_t the predictor has just stored;
+    the artificial viscosity is not added) into a second buffer, the two swap,
+    and K.apply_scalar_bc_heat3d relaxes T towards scalar_cylinder in the
+    forcing zone with the step's force_strength and sets the faces (inlet
+    scalar_inlet; outlet, adiabatic walls and spanwise faces copy).  The
+    scalar never acts back on the flow.  ``heat_history`` and
+    ``nusselt_numbers()`` read the per-step heat sums lazily; snapshots gain
+    T; tests/scalar3d_reference.py states the arithmetic.
+
     Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
     single sweeps: DESIGN.md 4.4), a periodic form of that Jacobi, masks that
     vary along z in the fused GS, pressure statistics (the step keeps no p), a
-    Strouhal estimate from the lift history, float64 and the slab path."""
+    Strouhal estimate from the lift history, T moments in the statistics,
+    buoyancy, float64 and the slab path."""
 
     _stats_span_default = True
 
@@ -1074,6 +1114,63 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         self.v.copy_(torch.from_numpy(v).to(self.device).expand_as(self.v))
         self._force = torch.zeros((1024, 3), dtype=torch.float64, device=self.device)
         self._dts = []
+        self.scalar = bool(cfg.scalar)
+        if self.scalar:
+            self.T = torch.full_like(self.u, float(np.float32(cfg.scalar_inlet)))
+            self._T_next = torch.empty_like(self.T)
+            self._heat = torch.zeros(1024, dtype=torch.float64, device=self.device)
+            # alpha = f32(nu / Pr), 1 / Pr_t = f32(1 / Pr_t): formed in double, rounded once
+            self._alpha = np.float32(float(cfg.nu) / cfg.prandtl)
+            self._inv_prt = np.float32(1.0 / cfg.turbulent_prandtl)
+
+    def _heat_slot(self):
+        k = len(self._energy_steps)
+        if k >= self._heat.numel():
+            grown = torch.zeros(2 * self._heat.numel(), dtype=torch.float64, device=self.device)
+            grown[:k] = self._heat[:k]
+            self._heat = grown
+        return self._heat[k:k + 1]
+
+    def _after_predictor(self, dt):
+        """The scalar's step: the advance with the step's incoming u, v, w
+        (and the nu_t the predictor has just stored), then the heating with the
+        step's force_strength and the faces; T and its second buffer swap."""
+        if not self.scalar:
+            return
+        cfg = self.config
+        K.scalar_advance3d(self.T, self.u, self.v, self.w, self._alpha, dt, cfg.dx, cfg.dy, cfg.dz, cfg.use_supg,
+                           nu_t=self.nu_t if self.use_les else None, inv_prt=self._inv_prt, out=self._T_next,
+                           periodic_z=self._periodic_z)
+        self.T, self._T_next = self._T_next, self.T
+        K.apply_scalar_bc_heat3d(self.T, self.ibm_mask, cfg.scalar_inlet, cfg.scalar_cylinder,
+                                 min(1.0, self.step / cfg.initial_steps), bbox=self.ibm_bbox,
+                                 heat_out=self._heat_slot(), periodic_z=self._periodic_z)
+
+    def _snapshot_fields(self):
+        return {"T": self.T} if self.scalar else {}
+
+    @property
+    def heat_history(self):
+        """[(step, Q)]: per step, the float64 sum of after - before of T over
+        the cells the heating changed, read lazily from the device (scalar=True)."""
+        if not self.scalar:
+            raise RuntimeError("heat_history: the scalar is off (CylinderChannel3DConfig(scalar=True))")
+        n = len(self._energy_steps)
+        vals = self._heat[:n].cpu().numpy() if n else np.zeros(0)
+        return [(s, float(q)) for s, q in zip(self._energy_steps, vals)]
+
+    def nusselt_numbers(self):
+        """[(step, Nu)] from heat_history: Nu = Q dx dy dz / (dt (nu / Pr)
+        (T_cyl - T_in) pi (z_max - z_min)) with the step's own dt -- the heat
+        the forcing adds per unit time over the conductive scale k dT (pi D
+        Lz) / D.  A volume-forcing estimate (the forcing zone is wider than
+        the cylinder and relaxes T rather than fixing a wall flux): the heat
+        counterpart of force_coefficients()."""
+        cfg = self.config
+        vol = cfg.dx * cfg.dy * cfg.dz
+        alpha = float(cfg.nu) / cfg.prandtl  # cfg.nu is a float32: the division in double
+        scale = alpha * (cfg.scalar_cylinder - cfg.scalar_inlet) * np.pi * (cfg.z_max - cfg.z_min)
+        return [(s, q * vol / (dt * scale)) for (s, q), dt in zip(self.heat_history, self._dts)]
 
     def solve_pressure_fast(self, div_u_star):
         """phi = zeros, then the masked solve (with cfg.dt, like v5.py:328-347):
@@ -1132,6 +1229,8 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
         super()._restart_histories()
         self._dts = []
         self._force.zero_()  # the forcing kernel adds into its step's row, and the rows are handed out from 0 again
+        if self.scalar:
+            self._heat.zero_()
 
     def compute_vorticity(self):
         """|omega| of the current fields: 0 on the six faces (periodic: the
@@ -1177,14 +1276,17 @@ def monitor_simulation_health3d(solver: LidDrivenCavity3DSolver, step: int) -> b
     (LidDrivenCavity3DSolver or CylinderChannel3DSolver):
     non-finite values, max|V| > max_velocity, max|div| above 20 (step <= 1000)
     or 2 (after); device reductions with one host read.  A spanwise-periodic
-    solver's divergence is the periodic one."""
+    solver's divergence is the periodic one; a solver that carries the passive
+    scalar (scalar=True) also needs T finite."""
     cfg = solver.config
     s = stream_handle()
     n = solver.u.numel()
     cnt = torch.zeros(2, dtype=torch.int32, device=solver.device)
     red = torch.zeros(2, dtype=torch.float32, device=solver.device)
     call("cfd_nonfinite_count_f32", ptr(solver.u), ptr(solver.v), n, ptr(cnt[0:1]), s)
-    call("cfd_nonfinite_count_f32", ptr(solver.w), None, n, ptr(cnt[1:2]), s)
+    # w, and the scalar T when the solver carries one
+    call("cfd_nonfinite_count_f32", ptr(solver.w), ptr(solver.T) if getattr(solver, "scalar", False) else None, n,
+         ptr(cnt[1:2]), s)
     for f in (solver.u, solver.v, solver.w):
         call("cfd_absmax_f32", ptr(f), n, ptr(red[0:1]), s)  # the max accumulates
     div = torch.empty_like(solver.u)

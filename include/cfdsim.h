@@ -596,6 +596,72 @@ int cfd_vorticity3d_zper_f32(const float *u, const float *v, const float *w, con
 int cfd_flow_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t,
                          double *acc, int nz, int ny, int nx, double weight, int span_average,
                          void *stream);
+/* Passive scalar (temperature) transport on (nz, ny, nx) float32 fields: the
+ * project's own arithmetic (the reference has no scalar), stated as NumPy in
+ * tests/scalar3d_reference.py and reproduced bit for bit.
+ *
+ * Advance.  On the interior cells T_new = T + dt*(-conv + lap) with conv and
+ * lap exactly cfd_predictor3d_f32's for one field f = T: advected by the
+ * cell's own (u, v, w), SUPG (tau formed with the diffusivity) or first-order
+ * upwind (use_supg = 0), and the cell's diffusivity ae in place of nu:
+ *   ae = alpha                       (nu_t NULL), or
+ *   ae = alpha + nu_t[c]*inv_prt     per cell in float32 (LES: inv_prt =
+ *                                    f32(1/Pr_t); inv_prt is ignored without nu_t).
+ * The six faces copy T through.  One launch: a plane march along z under the
+ * predictor's conditions (nx a multiple of the cells per lane, every array
+ * aligned to them, a plane below 2^31 bytes), else one thread per cell; both
+ * give the same bits.  T_new must not alias T, u, v, w or nu_t
+ * (CFD_E_INVALID before any launch); every dimension >= 3. */
+int cfd_scalar_advance3d_f32(const float *T, const float *u, const float *v, const float *w,
+                             float alpha, const float *nu_t, float inv_prt, float *T_new, int nz,
+                             int ny, int nx, double dx, double dy, double dz, float dt,
+                             int use_supg, void *stream);
+/* cfd_scalar_advance3d_f32 with a periodic z (the pad rule): every plane is
+ * interior in z, plane nz-1's U neighbour is plane 0; only the four x / y
+ * faces copy through.  nz even and >= 4. */
+int cfd_scalar_advance3d_zper_f32(const float *T, const float *u, const float *v, const float *w,
+                                  float alpha, const float *nu_t, float inv_prt, float *T_new,
+                                  int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                                  int use_supg, void *stream);
+/* Tuning of the scalar advance, per host thread (cleared by cfd_reset_tuning):
+ * variant 0 auto / 1 one thread per cell / 2 plane march (also at one cell per
+ * lane); rows per wave 0 (auto: 2), 1, 2; preferred cells per lane 0 (auto:
+ * 2), 1, 2, 4, halved until nx and the alignment fit; planes per chunk of the
+ * march, 0 = auto (8 .. 32). */
+int cfd_set_scalar3d_config(int variant, int rows, int cells_per_lane, int zchunk);
+/* The path of the calling thread's last scalar advance: 1 = plane march, 0 =
+ * one thread per cell, -1 = none yet; *cells_per_lane (optional) its cells
+ * per lane. */
+int cfd_get_last_scalar3d_path(int *cells_per_lane);
+/* Heating by the immersed boundary, then the scalar's faces, in place on T.
+ * Net effect, in this order:
+ *   1. on every cell (k, i, j) that is not a face cell (faces: rows 0 and
+ *      ny-1, columns 0 and nx-1, planes 0 and nz-1) with m = ibm_mask2d[i, j]
+ *      > 0:  T = (float)((double)T + (m*force_strength)*(t_cyl - (double)T)),
+ *      relaxation towards t_cyl (ibm_mask2d NULL: no heating);
+ *   2. spanwise faces, whole planes: T[0] = T[1], T[nz-1] = T[nz-2];
+ *   3. channel walls, adiabatic: row 0 = row 1, row ny-1 = row ny-2;
+ *   4. outlet: column nx-1 = column nx-2;
+ *   5. inlet: column 0 = f32(t_in), written last.
+ * Steps 2-5 are a gather: a face cell (k, i, j >= 1) ends with the heated
+ * value of (clamp(k, 1, nz-2), clamp(i, 1, ny-2), min(j, nx-2)).  Two
+ * launches: the heating visits the box [i0, i1) x [j0, j1) (cfd_apply_
+ * channel_bc_ibm3d_f32's box semantics: it contains every m > 0, the mask is
+ * read inside it only, any covering box gives the same bits) clipped to the
+ * non-face cells, one thread per cell; the faces are then written by one
+ * thread per face cell, which reads a non-face cell.  Neither passes over
+ * the grid.  heat_out (optional device double, added to, not zeroed): the sum
+ * of (double)after - (double)before over the heated cells, float64 per-thread
+ * sums, then the wave, the workgroup and one atomic per workgroup (skipped
+ * when its partial is 0); the order of the sum is not fixed. */
+int cfd_scalar_bc_heat3d_f32(float *T, const double *ibm_mask2d, int nz, int ny, int nx, double t_in,
+                             double t_cyl, double force_strength, int i0, int i1, int j0, int j1,
+                             double *heat_out, void *stream);
+/* cfd_scalar_bc_heat3d_f32 for a periodic z: no face planes -- the heating on
+ * all nz planes, then steps 3-5.  nz even and >= 4. */
+int cfd_scalar_bc_heat3d_zper_f32(float *T, const double *ibm_mask2d, int nz, int ny, int nx,
+                                  double t_in, double t_cyl, double force_strength, int i0, int i1,
+                                  int j0, int j1, double *heat_out, void *stream);
 
 /* --------------------------------------------------- float64 fields */
 /* memory_efficient=False (v5.py:287-296): every field float64; the kernels

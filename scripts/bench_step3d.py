@@ -50,6 +50,15 @@ element), the time those bytes take at the HBM peak and the fraction of the
 peak reached; then CylinderChannel3DSolver.time_step with statistics off, in
 span mode and in full mode, the three solvers alternating window by window.
 
+--scalar: the passive scalar leg instead, at the same grid:
+cfd_scalar_advance3d_f32 as plane march (auto, and every rows x cells-per-lane
+shape) and as per-cell kernel, with scalar alpha and with the nu_t array, SUPG
+and upwind, the fused predictor (SUPG, scalar nu, 24 B per cell) as the
+yardstick of the same session, cfd_scalar_bc_heat3d_f32 beside the BC + IBM
+stage, all alternating window by window (the advance at its algorithmic 20 B
+per cell, 24 B with nu_t); then CylinderChannel3DSolver.time_step with the
+scalar off and on, the two solvers alternating.
+
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
 `--les --sizes 512 --no-step`, `--les --sizes 1024 --no-step --check`, then
@@ -597,6 +606,120 @@ def stats_leg(rounds, launches, steps, step_only=False):
                           "energy_last": sv.energy_history[-1][1]}), flush=True)
 
 
+def scalar_leg(rounds, launches, steps, step_only=False):
+    """The passive scalar at the default 600 x 180 x 120 grid:
+    cfd_scalar_advance3d_f32 as plane march (auto and every (rows, cells per
+    lane)) and as per-cell kernel, scalar alpha and nu_t array, SUPG and
+    upwind, with the fused predictor (SUPG, scalar nu) as the yardstick of the
+    same session, then cfd_scalar_bc_heat3d_f32 beside the BC + IBM stage, the
+    legs alternating window by window; then CylinderChannel3DSolver.time_step
+    with the scalar off and on, the two solvers alternating."""
+    from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
+    c = CylinderChannel3DConfig()
+    nz, ny, nx = c.nz, c.ny, c.nx
+    cells = nz * ny * nx
+    grid = [nz, ny, nx]
+    if not step_only:
+        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=True, spanwise_perturbation=0.05, scalar=True))
+        for _ in range(2):
+            s.time_step()   # fields that depend on z, a nu_t and a heated T
+        out = torch.empty_like(s.T)
+        stars = [torch.empty_like(s.u) for _ in range(3)]
+        heat = torch.zeros(1, dtype=torch.float64, device="cuda")
+        paths = {}
+
+        def adv(label, cfg4, supg, nut):
+            def fn():
+                call("cfd_set_scalar3d_config", *cfg4)
+                K.scalar_advance3d(s.T, s.u, s.v, s.w, s._alpha, DT, c.dx, c.dy, c.dz, supg,
+                                   nu_t=s.nu_t if nut else None, inv_prt=s._inv_prt, out=out)
+                cpl = ctypes.c_int(0)
+                paths[label] = (int(_lib.lib().cfd_get_last_scalar3d_path(ctypes.byref(cpl))), int(cpl.value))
+            return fn
+
+        def pred():
+            K.predictor3d_fused(s.u, s.v, s.w, c.dx, c.dy, c.dz, DT, NU, True, u_star=stars[0], v_star=stars[1],
+                                w_star=stars[2], store_tau=False)
+
+        def bc_heat():
+            K.apply_scalar_bc_heat3d(out, s.ibm_mask, c.scalar_inlet, c.scalar_cylinder, 1.0, bbox=s.ibm_bbox,
+                                     heat_out=heat)
+
+        def bc_ibm():
+            K.apply_channel_bc_ibm3d(*stars, s._y_dev, s.ibm_mask, c.y_max, c.V_inf, 2000, 1.0, bbox=s.ibm_bbox)
+
+        cases = {}
+        for supg in (True, False):
+            for nut in (False, True):
+                tag = ("supg" if supg else "upwind") + ("_nu_t" if nut else "")
+                nb = (24 if nut else 20) * cells
+                cases[f"advance_march_{tag}"] = (adv(f"advance_march_{tag}", (0, 0, 0, 0), supg, nut), nb)
+                cases[f"advance_per_cell_{tag}"] = (adv(f"advance_per_cell_{tag}", (1, 0, 0, 0), supg, nut), nb)
+        for supg, nut, tag in ((True, False, "supg"), (True, True, "supg_nu_t"), (False, False, "upwind"),
+                               (False, True, "upwind_nu_t")):
+            for r in (2, 1):
+                for cpl in (4, 2, 1):
+                    k = f"advance_march_{tag}_r{r}_c{cpl}"
+                    cases[k] = (adv(k, (2, r, cpl, 0), supg, nut), (24 if nut else 20) * cells)
+        cases["predictor3d_supg"] = (pred, BYTES_PER_CELL * cells)
+        cases["scalar_bc_heat"] = (bc_heat, 0)
+        cases["channel_bc_ibm"] = (bc_ibm, 0)
+        ms = {k: [] for k in cases}
+        try:
+            for fn, _ in cases.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for k, (fn, _) in cases.items():
+                    ms[k].append(window_ms(fn, launches))
+        finally:
+            call("cfd_reset_tuning")
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, v in ms.items():
+            nbytes = cases[k][1]
+            rec = {"bench": "scalar3d_kernel", "grid": grid, "kernel": k, "ms": round(med[k], 4),
+                   "ms_min": round(min(v), 4), "ms_max": round(max(v), 4), "windows_ms": [round(x, 4) for x in v],
+                   "rounds": rounds, "launches_per_round": launches}
+            if k in paths:
+                rec["path"], rec["cells_per_lane"] = paths[k]
+            if nbytes:
+                rec.update({"algorithmic_bytes": nbytes, "ms_at_hbm_peak": round(nbytes / HBM_PEAK * 1e3, 4),
+                            "hbm_fraction": round(nbytes / (med[k] * 1e-3) / HBM_PEAK, 4)})
+            print(json.dumps(rec), flush=True)
+        for tag in ("supg", "supg_nu_t", "upwind", "upwind_nu_t"):
+            m, p = ms[f"advance_march_{tag}"], ms[f"advance_per_cell_{tag}"]
+            spread = max(max(m) - min(m), max(p) - min(p))
+            gain = statistics.median(p) - statistics.median(m)
+            print(json.dumps({"bench": "scalar3d_march_vs_per_cell", "mode": tag,
+                              "per_cell_over_march": round(statistics.median(p) / statistics.median(m), 3),
+                              "gain_ms": round(gain, 4), "window_spread_ms": round(spread, 4),
+                              "march_is_default_by_rule": bool(gain > spread),
+                              "march_over_predictor": round(statistics.median(m) / med["predictor3d_supg"], 3)}),
+                  flush=True)
+        del s, out, stars, cases
+        torch.cuda.empty_cache()
+    solvers = {}
+    for k, on in (("off", False), ("on", True)):
+        sv = solvers[k] = CylinderChannel3DSolver(CylinderChannel3DConfig(spanwise_perturbation=0.05, scalar=on))
+        for _ in range(2):
+            sv.time_step()
+    torch.cuda.synchronize()
+    st = {k: [] for k in solvers}
+    for _ in range(rounds):
+        for k, sv in solvers.items():
+            st[k].append(window_ms(sv.time_step, steps))
+    med = {k: statistics.median(v) for k, v in st.items()}
+    for k, sv in solvers.items():
+        print(json.dumps({"bench": "scalar3d_time_step", "grid": grid, "scalar": k, "les": False, "pressure": "rbgs",
+                          "iterations": c.pressure_iterations, "steps_per_window": steps, "rounds": rounds,
+                          "ms_per_step": round(med[k], 3), "ms_min": round(min(st[k]), 3),
+                          "ms_max": round(max(st[k]), 3), "windows_ms": [round(x, 3) for x in st[k]],
+                          "delta_ms_over_off": round(med[k] - med["off"], 3),
+                          "heat_last": sv.heat_history[-1][1] if k == "on" else None,
+                          "energy_last": sv.energy_history[-1][1]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="512,1024")
@@ -613,9 +736,14 @@ def main():
                     help="with --cylinder: only the predictor and time_step pairs of the periodic leg")
     ap.add_argument("--stats", action="store_true", help="the flow statistics leg (see above) and nothing else")
     ap.add_argument("--stats-step-only", action="store_true", help="with --stats: only the three time_step timings")
+    ap.add_argument("--scalar", action="store_true", help="the passive scalar leg (see above) and nothing else")
+    ap.add_argument("--scalar-step-only", action="store_true", help="with --scalar: only the two time_step timings")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_step3d.py needs the GPU")
+    if a.scalar:
+        scalar_leg(a.rounds, a.launches, 3, a.scalar_step_only)
+        return
     if a.stats:
         stats_leg(a.rounds, a.launches, 3, a.stats_step_only)
         return
