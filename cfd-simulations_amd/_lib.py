@@ -130,6 +130,7 @@ PROTOTYPES = {
     "cfd_vorticity3d_zper_f32": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
                                          c_double, P]),
     "cfd_flow_stats3d_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_double, c_int, P]),
+    "cfd_flow_scalar_stats3d_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_double, c_int, P]),
     "cfd_supg_tau2d_f64": (c_int, [P, P, P, c_double, P, c_int, c_int, c_double, c_double, c_double, P]),
     "cfd_convection_supg2d_f64": (c_int, [P, P, P, P, P, c_int, c_int, c_double, c_double, P]),
     "cfd_convection_upwind2d_f64": (c_int, [P, P, P, P, c_int, c_int, c_double, c_double, P]),

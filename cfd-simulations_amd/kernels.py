@@ -28,6 +28,7 @@ __all__ = [
     "predictor3d_fused_les", "compute_smagorinsky_viscosity3d",
     "apply_channel_bc_ibm3d", "compute_vorticity3d", "solve_pressure_gauss_seidel3d_zper",
     "accumulate_flow_stats3d", "scalar_advance3d", "apply_scalar_bc_heat3d",
+    "accumulate_flow_scalar_stats3d",
 ]
 
 
@@ -670,6 +671,23 @@ def accumulate_flow_stats3d(u, v, w, acc, weight, span_average, nu_t=None):
                          f"on {acc.device}")
     call("cfd_flow_stats3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), ptr(acc), nz, ny, nx, float(weight),
          1 if span_average else 0, stream_handle())
+    return acc
+
+
+def accumulate_flow_scalar_stats3d(u, v, w, T, acc, weight, span_average, nu_t=None):
+    """accumulate_flow_stats3d with the scalar ``T`` (cfd_flow_scalar_stats3d_f32):
+    after its moments (u .. vw, then nu_t when given) come T, TT, uT, vT, wT,
+    so ``acc`` has 14 planes, or 15 with ``nu_t``.  The first 9 (10) planes
+    get exactly the bits accumulate_flow_stats3d gives them.  ``T`` may be
+    one of u, v, w.  Returns acc."""
+    nz, ny, nx = _fields3d(u, v=v, w=w, nu_t=nu_t, T=T)
+    nm = 14 if nu_t is None else 15
+    want = (nm, ny, nx) if span_average else (nm, nz, ny, nx)
+    if acc.dtype != torch.float64 or tuple(acc.shape) != want or acc.device != u.device:
+        raise ValueError(f"acc must be a float64 {want} array on {u.device}, got {tuple(acc.shape)} {acc.dtype} "
+                         f"on {acc.device}")
+    call("cfd_flow_scalar_stats3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), ptr(T), ptr(acc), nz, ny, nx,
+         float(weight), 1 if span_average else 0, stream_handle())
     return acc
 
 

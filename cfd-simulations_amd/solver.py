@@ -571,12 +571,28 @@ class LesCavity3DConfig(LidDrivenCavity3DConfig):
 
 
 STATS_MOMENTS = ("u", "v", "w", "uu", "vv", "ww", "uv", "uw", "vw", "nu_t")
+STATS_SCALAR_MOMENTS = ("T", "TT", "uT", "vT", "wT")  # behind the 9 or 10 above with scalar_moments
 
 
-def derive_statistics(sums, weight, nz, span_average):
+def derive_statistics(sums, weight, nz, span_average, scalar=False):
     """The averages of the float64 moment sums (STATS_MOMENTS' order; 9 or 10
     planes): every sum over weight * nz (span_average) or weight, the Reynolds
-    stresses <ab> - <a><b>, tke = ((uu + vv) + ww) / 2."""
+    stresses <ab> - <a><b>, tke = ((uu + vv) + ww) / 2.  ``scalar``: the sums
+    end with STATS_SCALAR_MOMENTS' five planes (14 or 15 in all) and the
+    result gains mean_T, the variance TT = <TT> - <T>^2 and the turbulent heat
+    fluxes uT, vT, wT = <aT> - <a><T>."""
+    sums = np.asarray(sums, np.float64)
+    if sums.shape[0] not in ((14, 15) if scalar else (9, 10)):
+        raise ValueError(f"derive_statistics: {sums.shape[0]} moment planes with scalar={bool(scalar)}")
+    if scalar:
+        out = derive_statistics(sums[:-5], weight, nz, span_average)
+        norm = np.float64(weight) * np.float64(nz) if span_average else np.float64(weight)
+        t = sums[-5:] / norm
+        out["mean_T"] = t[0]
+        out["TT"] = t[1] - t[0] * t[0]
+        for q, name in enumerate(("uT", "vT", "wT")):
+            out[name] = t[2 + q] - out["mean_" + name[0]] * t[0]
+        return out
     norm = np.float64(weight) * np.float64(nz) if span_average else np.float64(weight)
     m = np.asarray(sums, np.float64) / norm
     out = {"weight": float(weight), "mean_u": m[0], "mean_v": m[1], "mean_w": m[2]}
@@ -610,8 +626,9 @@ class LidDrivenCavity3DSolver:
     vv, ww, uv, uw, vw (and nu_t with LES) of the step's final, clipped
     fields, one K.accumulate_flow_stats3d launch per sampled step, per cell or
     summed over z; ``statistics()`` derives the means, the Reynolds stresses
-    and the turbulent kinetic energy.  With statistics off time_step launches
-    what it launched without them.
+    and the turbulent kinetic energy.  A solver that carries the passive
+    scalar can add T, TT, uT, vT, wT (``scalar_moments=True``).  With
+    statistics off time_step launches what it launched without them.
 
     Snapshots: ``save_snapshot`` / ``load_snapshot`` keep the 2-D solver's
     .npz layout (groups step_%06d, appended) with u, v, w, phi, |omega|, the
@@ -627,6 +644,7 @@ class LidDrivenCavity3DSolver:
     _periodic_z = False  # CylinderChannel3DSolver with spanwise_bc="periodic": the *_zper stages
     _stats_span_default = False  # enable_statistics(span_average=None); the cylinder channel: True
     _stats = None  # (start_step, interval, span_average, weight) once statistics are enabled
+    _stats_scalar = False  # enable_statistics(scalar_moments=True): T, TT, uT, vT, wT behind the flow moments
 
     def __init__(self, config: LidDrivenCavity3DConfig):
         self.config = cfg = config
@@ -777,7 +795,7 @@ class LidDrivenCavity3DSolver:
         return dt
 
     # -------------------------------------------------------- statistics
-    def enable_statistics(self, start_step=0, interval=1, span_average=None, weight="dt"):
+    def enable_statistics(self, start_step=0, interval=1, span_average=None, weight="dt", scalar_moments=False):
         """Accumulate the flow moments of the clipped u, v, w (with LES also
         nu_t) at the end of every step k >= start_step with (k - start_step) %
         interval == 0, into zeroed float64 sums on the device.
@@ -785,26 +803,35 @@ class LidDrivenCavity3DSolver:
         cavity): sum over z into (ny, nx) planes instead of keeping
         (nz, ny, nx).  ``weight``: "dt" weights a sample by its step's dt
         (the dt is adaptive from step 1000 on, so equal weights would bias a
-        time average), "sample" by 1.0.  Calling it again with the same
-        settings does nothing; other settings raise ValueError unless
-        reset_statistics() came first."""
+        time average), "sample" by 1.0.  ``scalar_moments`` (a solver that
+        carries the passive scalar T, else ValueError): the sums gain T, TT,
+        uT, vT, wT of the step's final T as five further planes, in the same
+        single launch (K.accumulate_flow_scalar_stats3d).  Calling it again
+        with the same settings does nothing; other settings raise ValueError
+        unless reset_statistics() came first."""
         if span_average is None:
             span_average = self._stats_span_default
         if weight not in ("dt", "sample"):
             raise ValueError(f"enable_statistics: weight must be 'dt' or 'sample', not {weight!r}")
         if int(start_step) < 0 or int(interval) < 1:
             raise ValueError(f"enable_statistics: start_step >= 0 and interval >= 1 (got {start_step}, {interval})")
+        scalar_moments = bool(scalar_moments)
+        if scalar_moments and not getattr(self, "scalar", False):
+            raise ValueError("enable_statistics: scalar_moments needs a solver that carries the passive scalar "
+                             "(CylinderChannel3DConfig(scalar=True))")
         settings = (int(start_step), int(interval), bool(span_average), weight)
         if self._stats is not None:
-            if settings == self._stats:
+            if settings == self._stats and scalar_moments == self._stats_scalar:
                 return
             if not self._stats_reset:
-                raise ValueError(f"enable_statistics: statistics are on with {self._stats}, asked for {settings}; "
+                raise ValueError(f"enable_statistics: statistics are on with {self._stats}, scalar_moments="
+                                 f"{self._stats_scalar}, asked for {settings}, scalar_moments={scalar_moments}; "
                                  "call reset_statistics() first")
         cfg = self.config
-        nm = 10 if self.use_les else 9
+        nm = (10 if self.use_les else 9) + (5 if scalar_moments else 0)
         shape = (nm, cfg.ny, cfg.nx) if settings[2] else (nm, cfg.nz, cfg.ny, cfg.nx)
         self._stats = settings
+        self._stats_scalar = scalar_moments
         self._stats_sums = torch.zeros(shape, dtype=torch.float64, device=self.device)
         self._stats_weight = np.float64(0.0)
         self._stats_samples = 0
@@ -826,8 +853,11 @@ class LidDrivenCavity3DSolver:
         if k < start or (k - start) % interval:
             return
         wgt = float(dt) if mode == "dt" else 1.0
-        K.accumulate_flow_stats3d(self.u, self.v, self.w, self._stats_sums, wgt, span,
-                                  nu_t=self.nu_t if self.use_les else None)
+        nu_t = self.nu_t if self.use_les else None
+        if self._stats_scalar:  # the step's final T: after the advance, the heating and the faces
+            K.accumulate_flow_scalar_stats3d(self.u, self.v, self.w, self.T, self._stats_sums, wgt, span, nu_t=nu_t)
+        else:
+            K.accumulate_flow_stats3d(self.u, self.v, self.w, self._stats_sums, wgt, span, nu_t=nu_t)
         self._stats_weight = self._stats_weight + np.float64(wgt)
         self._stats_samples += 1
         self._stats_reset = False
@@ -837,13 +867,14 @@ class LidDrivenCavity3DSolver:
         ``samples``, ``weight`` (the total), ``mean_u``, ``mean_v``,
         ``mean_w``, the Reynolds stresses ``uu``, ``vv``, ``ww``, ``uv``,
         ``uw``, ``vw`` as <ab> - <a><b>, ``tke`` = (uu + vv + ww) / 2 and,
-        with LES, ``mean_nu_t``.  Shapes: (ny, nx) with span_average (the sums
-        over weight * nz), else (nz, ny, nx) (over weight).  RuntimeError
-        before the first sample."""
+        with LES, ``mean_nu_t``; with scalar_moments also ``mean_T``, the
+        variance ``TT`` and the turbulent heat fluxes ``uT``, ``vT``, ``wT``.
+        Shapes: (ny, nx) with span_average (the sums over weight * nz), else
+        (nz, ny, nx) (over weight).  RuntimeError before the first sample."""
         if self._stats is None or self._stats_samples == 0:
             raise RuntimeError("statistics(): no sample yet (enable_statistics, then time_step)")
         sums = self._stats_sums.cpu().numpy()  # the one device read
-        out = derive_statistics(sums, self._stats_weight, self.config.nz, self._stats[2])
+        out = derive_statistics(sums, self._stats_weight, self.config.nz, self._stats[2], scalar=self._stats_scalar)
         out["samples"] = self._stats_samples
         return out
 
@@ -859,9 +890,11 @@ class LidDrivenCavity3DSolver:
         the axes x, y, z, time, solver_step, nu_t with LES and, when
         statistics are enabled, stats_sums, stats_weight, stats_samples and
         the four settings (stats_start_step, stats_interval,
-        stats_span_average, stats_weight_mode).  An existing file keeps its
-        groups and gains this one as appended zip members; a group already
-        present is left alone without reading the device."""
+        stats_span_average, stats_weight_mode), and with scalar_moments
+        stats_scalar_moments (stats_sums then has 14 or 15 planes; a group
+        without that member was written without them).  An existing file
+        keeps its groups and gains this one as appended zip members; a group
+        already present is left alone without reading the device."""
         g = f"step_{step:06d}"
         if _npz_has_group(path, g):
             return
@@ -883,6 +916,8 @@ class LidDrivenCavity3DSolver:
                            f"{g}/stats_samples": np.int64(self._stats_samples),
                            f"{g}/stats_start_step": np.int64(start), f"{g}/stats_interval": np.int64(interval),
                            f"{g}/stats_span_average": np.bool_(span), f"{g}/stats_weight_mode": np.array(mode)})
+            if self._stats_scalar:
+                groups[f"{g}/stats_scalar_moments"] = np.bool_(True)
         groups.update({f"{g}/{name}": host(t) for name, t in self._snapshot_fields().items()})
         _npz_append(path, groups)
 
@@ -895,11 +930,11 @@ class LidDrivenCavity3DSolver:
         """Restart from a save_snapshot file: group step_%06d (the latest
         when ``step`` is None) gives u, v, w, phi, nu_t (LES), the step counter
         and, if the group holds them, the statistics: they are enabled with
-        the stored settings if they are off, and a solver whose statistics are
-        on with other settings raises ValueError, as does a file of another
-        grid shape.  Returns the stored time.  The histories (energy, forces)
-        start empty, on a solver that has already stepped too.  Two cases are
-        accepted and fall outside the guarantee below: a group without nu_t
+        the stored settings (scalar_moments among them) if they are off, and a
+        solver whose statistics are on with other settings raises ValueError,
+        as does a file of another grid shape or moment count.  Returns the
+        stored time.  The histories (energy, forces) start empty, on a solver
+        that has already stepped too.  Two cases are accepted and fall outside the guarantee below: a group without nu_t
         (written with LES off) leaves an LES solver's nu_t as it is, which
         the adaptive dt reads from step 1000 on; a group without statistics
         (written with them off) leaves the solver's running sums, weight and
@@ -918,11 +953,17 @@ class LidDrivenCavity3DSolver:
             if has_stats:
                 settings = (int(f[f"{g}/stats_start_step"]), int(f[f"{g}/stats_interval"]),
                             bool(f[f"{g}/stats_span_average"]), str(f[f"{g}/stats_weight_mode"]))
-                if self._stats is not None and self._stats != settings:
-                    raise ValueError(f"{path}: {g} holds statistics with {settings}, the solver's are on with "
-                                     f"{self._stats}")
+                key = f"{g}/stats_scalar_moments"
+                scalar_moments = bool(f[key]) if key in f.files else False
+                if self._stats is not None and (self._stats != settings or self._stats_scalar != scalar_moments):
+                    raise ValueError(f"{path}: {g} holds statistics with {settings}, scalar_moments="
+                                     f"{scalar_moments}, the solver's are on with {self._stats}, scalar_moments="
+                                     f"{self._stats_scalar}")
+                if scalar_moments and not getattr(self, "scalar", False):
+                    raise ValueError(f"{path}: {g} holds statistics with scalar moments, the solver carries no "
+                                     "scalar")
                 sums = f[f"{g}/stats_sums"]
-                nm = 10 if self.use_les else 9
+                nm = (10 if self.use_les else 9) + (5 if scalar_moments else 0)
                 want = (nm, cfg.ny, cfg.nx) if settings[2] else (nm, *shape)
                 if sums.shape != want:
                     raise ValueError(f"{path}: {g} holds {sums.shape} statistics sums, the solver {want}")
@@ -935,7 +976,7 @@ class LidDrivenCavity3DSolver:
                     t.copy_(torch.from_numpy(f[f"{g}/{name}"]))
             if has_stats:
                 if self._stats is None:
-                    self.enable_statistics(*settings)
+                    self.enable_statistics(*settings, scalar_moments=scalar_moments)
                 self._stats_sums.copy_(torch.from_numpy(sums))
                 self._stats_weight = np.float64(f[f"{g}/stats_weight"])
                 self._stats_samples = int(f[f"{g}/stats_samples"])
@@ -1058,6 +1099,11 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     statistics, save_snapshot, load_snapshot); here the statistics default to
     the span average, the mean flow and Reynolds stresses over time and z on
     the (ny, nx) plane, and a snapshot's vorticity is NaN in the cylinder.
+    With the scalar on, ``enable_statistics(scalar_moments=True)`` adds T, TT,
+    uT, vT, wT of the step's final T to the sums in the same single launch
+    (K.accumulate_flow_scalar_stats3d) and ``statistics()`` gains mean_T, the
+    temperature variance TT and the turbulent heat fluxes uT, vT, wT; off by
+    default, and then the sums, snapshots and launches are what they were.
 
     Passive scalar (config.scalar=True; off by default, and then nothing is
     allocated or launched): ``T`` starts at scalar_inlet.  Each step, directly
@@ -1075,8 +1121,8 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
     single sweeps: DESIGN.md 4.4), a periodic form of that Jacobi, masks that
     vary along z in the fused GS, pressure statistics (the step keeps no p), a
-    Strouhal estimate from the lift history, T moments in the statistics,
-    buoyancy, float64 and the slab path."""
+    Strouhal estimate from the lift history, buoyancy, float64 and the slab
+    path."""
 
     _stats_span_default = True
 

@@ -596,6 +596,18 @@ int cfd_vorticity3d_zper_f32(const float *u, const float *v, const float *w, con
 int cfd_flow_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t,
                          double *acc, int nz, int ny, int nx, double weight, int span_average,
                          void *stream);
+/* cfd_flow_stats3d_f32 with a scalar field T (the temperature): after its
+ * moments (u .. vw, then nu_t when given) come T, TT, uT, vT, wT, so nm = 14,
+ * or 15 with nu_t; acc is (nm, nz, ny, nx) or, span_average = 1, (nm, ny, nx).
+ * The same arithmetic and the same order of every sum: the first 9 (10) planes
+ * of acc get exactly the bits cfd_flow_stats3d_f32 gives on the same u, v, w
+ * (nu_t), weight and prior acc, in both modes, and the result is the same run
+ * to run.  No atomics, no allocation, no workspace.  nu_t may be NULL.  T may
+ * be one of u, v, w (everything but acc is only read); u, v, w must be three
+ * arrays; weight finite. */
+int cfd_flow_scalar_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t,
+                                const float *T, double *acc, int nz, int ny, int nx,
+                                double weight, int span_average, void *stream);
 /* Passive scalar (temperature) transport on (nz, ny, nx) float32 fields: the
  * project's own arithmetic (the reference has no scalar), stated as NumPy in
  * tests/scalar3d_reference.py and reproduced bit for bit.

@@ -47,8 +47,12 @@ moment plane per column, or per cell), and cfd_vorticity3d_f32 writing |omega|
 only as the yardstick of the same session, alternating window by window, each
 with its algorithmic bytes (the fields read once, 16 B per accumulator
 element), the time those bytes take at the HBM peak and the fraction of the
-peak reached; then CylinderChannel3DSolver.time_step with statistics off, in
-span mode and in full mode, the three solvers alternating window by window.
+peak reached; the same with the scalar's moments (cfd_flow_scalar_stats3d_f32:
+span with T, span with nu_t and T, full with T) and the fused launch's time
+over the nm = 9 span launch's, against the two launches a separate T pass would
+need; then CylinderChannel3DSolver.time_step with statistics off, in span mode
+and in full mode, and on a scalar=True solver with statistics off and with
+scalar_moments in span mode, the five solvers alternating window by window.
 
 --scalar: the passive scalar leg instead, at the same grid:
 cfd_scalar_advance3d_f32 as plane march (auto, and every rows x cells-per-lane
@@ -528,24 +532,28 @@ def cylinder_leg(rounds, launches, steps):
         torch.cuda.empty_cache()
 
 
-def stats_leg(rounds, launches, steps, step_only=False):
+def stats_leg(rounds, launches, steps, step_only=False, no_step=False):
     """The flow statistics at the default 600 x 180 x 120 grid:
     cfd_flow_stats3d_f32 in span mode without and with nu_t and in full mode,
     with cfd_vorticity3d_f32 (|omega| only, masked) as the yardstick, the legs
-    alternating window by window; then CylinderChannel3DSolver.time_step with
-    statistics off, in span mode and in full mode, the solvers alternating."""
+    alternating window by window, cfd_flow_scalar_stats3d_f32 (T's moments
+    in the same launch: nm = 14, 15) among them; then
+    CylinderChannel3DSolver.time_step with statistics off, in span mode and in
+    full mode, and with the scalar on without statistics and with
+    scalar_moments in span mode, the solvers alternating."""
     from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
     c = CylinderChannel3DConfig()
     nz, ny, nx = c.nz, c.ny, c.nx
     cells, cols = nz * ny * nx, ny * nx
     grid = [nz, ny, nx]
     if not step_only:
-        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=True, spanwise_perturbation=0.05))
+        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=True, spanwise_perturbation=0.05, scalar=True))
         for _ in range(2):
-            s.time_step()   # fields that depend on z, and a nu_t
+            s.time_step()   # fields that depend on z, a nu_t and a heated T (the scalar is passive: u, v, w as without)
         mag = torch.empty_like(s.u)
-        span9, span10 = (torch.zeros((nm, ny, nx), dtype=torch.float64, device="cuda") for nm in (9, 10))
-        full9 = torch.zeros((9, nz, ny, nx), dtype=torch.float64, device="cuda")
+        span9, span10, span14, span15 = (torch.zeros((nm, ny, nx), dtype=torch.float64, device="cuda")
+                                         for nm in (9, 10, 14, 15))
+        full9, full14 = (torch.zeros((nm, nz, ny, nx), dtype=torch.float64, device="cuda") for nm in (9, 14))
 
         def vort():
             call("cfd_vorticity3d_f32", _lib.ptr(s.u), _lib.ptr(s.v), _lib.ptr(s.w), _lib.ptr(s.cylinder_mask), None,
@@ -558,6 +566,12 @@ def stats_leg(rounds, launches, steps, step_only=False):
                                                                        nu_t=s.nu_t), 16 * cells + 16 * 10 * cols),
                  "stats_full": (lambda: K.accumulate_flow_stats3d(s.u, s.v, s.w, full9, 2e-5, False),
                                 (12 + 16 * 9) * cells),
+                 "scalar_stats_span": (lambda: K.accumulate_flow_scalar_stats3d(s.u, s.v, s.w, s.T, span14, 2e-5,
+                                                                                True), 16 * cells + 16 * 14 * cols),
+                 "scalar_stats_span_nu_t": (lambda: K.accumulate_flow_scalar_stats3d(
+                     s.u, s.v, s.w, s.T, span15, 2e-5, True, nu_t=s.nu_t), 20 * cells + 16 * 15 * cols),
+                 "scalar_stats_full": (lambda: K.accumulate_flow_scalar_stats3d(s.u, s.v, s.w, s.T, full14, 2e-5,
+                                                                                False), (16 + 16 * 14) * cells),
                  "vorticity3d": (vort, 17 * cells)}      # u, v, w and the mask read, |omega| written
         ms = {k: [] for k in cases}
         for fn, _ in cases.values():
@@ -580,14 +594,29 @@ def stats_leg(rounds, launches, steps, step_only=False):
         print(json.dumps({"bench": "stats3d_span_vs_vorticity", "span_over_vorticity":
                           round(med["stats_span"] / med["vorticity3d"], 3), "window_spread_ms": round(spread, 4),
                           "span_not_slower": bool(med["stats_span"] <= med["vorticity3d"] + spread)}), flush=True)
-        del s, mag, span9, span10, full9, cases
+        # the fused nm = 14 launch against two launches: a separate pass for T's five moments would read
+        # u, v, w and T again, more bytes than the nm = 9 pass itself, so two launches cost at least 2x it
+        a, b = ms["scalar_stats_span"], ms["stats_span"]
+        spread = max(max(a) - min(a), max(b) - min(b))
+        print(json.dumps({"bench": "stats3d_scalar_span_vs_span", "fused_over_span9":
+                          round(med["scalar_stats_span"] / med["stats_span"], 3),
+                          "byte_model_ratio": round(cases["scalar_stats_span"][1] / cases["stats_span"][1], 3),
+                          "margin_ms_under_twice_span9": round(2 * med["stats_span"] - med["scalar_stats_span"], 4),
+                          "window_spread_ms": round(spread, 4),
+                          "fused_ships_by_rule": bool(2 * med["stats_span"] - med["scalar_stats_span"] > spread)}),
+              flush=True)
+        del s, mag, span9, span10, span14, span15, full9, full14, cases
         torch.cuda.empty_cache()
-    modes = {"off": None, "span": True, "full": False}
+    if no_step:   # --no-step: the kernels only
+        return
+    # statistics: (span_average or None for off, scalar on, scalar_moments)
+    modes = {"off": (None, False, False), "span": (True, False, False), "full": (False, False, False),
+             "scalar_off": (None, True, False), "scalar_span_moments": (True, True, True)}
     solvers = {}
-    for k, span in modes.items():
-        sv = solvers[k] = CylinderChannel3DSolver(CylinderChannel3DConfig(spanwise_perturbation=0.05))
+    for k, (span, scalar, moments) in modes.items():
+        sv = solvers[k] = CylinderChannel3DSolver(CylinderChannel3DConfig(spanwise_perturbation=0.05, scalar=scalar))
         if span is not None:
-            sv.enable_statistics(span_average=span)
+            sv.enable_statistics(span_average=span, scalar_moments=moments)
         for _ in range(2):
             sv.time_step()
     torch.cuda.synchronize()
@@ -601,8 +630,9 @@ def stats_leg(rounds, launches, steps, step_only=False):
                           "pressure": "rbgs", "iterations": c.pressure_iterations, "steps_per_window": steps,
                           "rounds": rounds, "ms_per_step": round(med[k], 3), "ms_min": round(min(st[k]), 3),
                           "ms_max": round(max(st[k]), 3), "windows_ms": [round(x, 3) for x in st[k]],
-                          "delta_ms_over_off": round(med[k] - med["off"], 3),
-                          "samples": 0 if k == "off" else sv.statistics()["samples"],
+                          "scalar": modes[k][1], "scalar_moments": modes[k][2],
+                          "delta_ms_over_off": round(med[k] - med["scalar_off" if modes[k][1] else "off"], 3),
+                          "samples": 0 if modes[k][0] is None else sv.statistics()["samples"],
                           "energy_last": sv.energy_history[-1][1]}), flush=True)
 
 
@@ -735,7 +765,7 @@ def main():
     ap.add_argument("--zper-only", action="store_true",
                     help="with --cylinder: only the predictor and time_step pairs of the periodic leg")
     ap.add_argument("--stats", action="store_true", help="the flow statistics leg (see above) and nothing else")
-    ap.add_argument("--stats-step-only", action="store_true", help="with --stats: only the three time_step timings")
+    ap.add_argument("--stats-step-only", action="store_true", help="with --stats: only the five time_step timings")
     ap.add_argument("--scalar", action="store_true", help="the passive scalar leg (see above) and nothing else")
     ap.add_argument("--scalar-step-only", action="store_true", help="with --scalar: only the two time_step timings")
     a = ap.parse_args()
@@ -745,7 +775,7 @@ def main():
         scalar_leg(a.rounds, a.launches, 3, a.scalar_step_only)
         return
     if a.stats:
-        stats_leg(a.rounds, a.launches, 3, a.stats_step_only)
+        stats_leg(a.rounds, a.launches, 3, a.stats_step_only, a.no_step)
         return
     if a.cylinder:
         if not a.zper_only:

@@ -16,7 +16,7 @@ out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--of
                       "-Rpass-analysis=kernel-resource-usage", *extra], capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
-    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|VGPRs Spill|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|SGPRs): (\S+)", line)
+    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|VGPRs Spill|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]|SGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]): (\S+)", line)
     if not m:
         continue
     k, v = m.group(1), m.group(2)
@@ -27,5 +27,6 @@ for line in out.splitlines():
         cur[k.split(" ")[0] + ("_spill" if "Spill" in k else "")] = v
 for r in rows:
     if flt in r["name"]:
-        print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("VGPRs_spill","?"):>3} spill {r.get("LDS","?"):>6} lds '
+        print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("VGPRs_spill","?"):>3} spill {r.get("TotalSGPRs","?"):>4} sgpr '
+              f'{r.get("ScratchSize","?"):>3} scratch {r.get("LDS","?"):>6} lds '
               f'occ {r.get("Occupancy","?")}  {r["name"][:150]}')
