@@ -19,7 +19,7 @@
 // The K = 4 Jacobi pass (LDS-DMA path) differs in two places.  Level 0 is
 // not copied in phase W: its tile is the DMA slot the plane landed in (T0S).
 // And the halo wave issues its global loads after the first barrier, not at
-// the step's start (CFD_TBR_HLD = 2).  Issued at the start, with its phase-W
+// the step's start (HLD = 2).  Issued at the start, with its phase-W
 // stores behind them in program order, the halo wave reached the first
 // barrier last (per-wave trace: ~2200 cycles into a ~5500-cycle step, the
 // row waves after 700-1350) -- presumably its loads wait for a place in the
@@ -27,14 +27,8 @@
 // moment.  Nothing reads the loaded rows before the queues shift at the end
 // of the step, where the halo wave has ~1000 cycles of slack.
 //
-// A variant kept behind CFD_TBR_T1D (off: measured slower) double-buffers
-// T_1 so that the row waves store level 1 in phase R: step z reads level 1
-// of plane z - 1 in buffer (z - zs) & 1 and stores level 1 of plane z into
-// the other one, which was last read in phase R of step z - 1 and is next
-// read in phase R of step z + 1 -- the existing end-of-step barriers (and
-// the phase-W barriers behind them) separate both, no barrier is added.
-// The halo wave keeps storing its level-1 chunks in phase W, into the buffer
-// that step reads.  See DESIGN.md ("K = 4: what bounds phase W").
+// (Tried there: a second T_1 buffer, the row waves storing level 1 in phase R.  It measured slower;
+// commit b331167 last held it, DESIGN.md "K = 4: what bounds phase W" has the numbers.)
 //
 // Shapes (K, row waves, rows per wave) -> output rows W = NWR*RPW + 2 - 2K:
 // (3, 11, 2) W = 18; (4, 7, 3) W = 15; (3, 7, 3) W = 17.  Everything else --
@@ -42,6 +36,7 @@
 // is as in that design, and the result is bit-identical to K single
 // sweeps (tests/test_gpu_parity.py).
 #include <type_traits>
+#include <utility>
 
 #include "internal.hpp"
 
@@ -97,42 +92,6 @@ __device__ inline __amdgpu_buffer_rsrc_t plane_rsrc(const float *base, int p, in
 // as well: 2.97 ms at K = 3 -- the neighbouring tiles' halo re-reads then
 // miss L2.)
 constexpr int kStoreNt = 2;
-// lane-based LDS addressing and exact vmcnt waits in the Jacobi row waves
-// (A/B knobs; see the DMA row wave)
-#ifndef CFD_TBR_LB
-#define CFD_TBR_LB 1
-#endif
-#ifndef CFD_TBR_XW
-#define CFD_TBR_XW 1
-#endif
-#ifndef CFD_TBR_SD  // per-step scalar state by additions (Jacobi row waves; see the DMA row wave)
-#define CFD_TBR_SD 1
-#endif
-#ifndef CFD_TBR_T0S  // level-0 tile = the DMA staging slot (Jacobi; see jacobi3d_tbr)
-#define CFD_TBR_T0S 1
-#endif
-#ifndef CFD_TBR_EARLY
-#define CFD_TBR_EARLY 1
-#endif
-#ifndef CFD_TBR_ROT3  // K = 4 Jacobi: level queues rotated with period 3 (see jacobi3d_tbr)
-#define CFD_TBR_ROT3 1
-#endif
-#ifndef CFD_TBR_MSTEP  // kMask2d: the mask tests formed per z-step (see the DMA row wave)
-#define CFD_TBR_MSTEP 1
-#endif
-#ifndef CFD_TBR_V1  // ROT3: level 0 lives in the slot ring only (see the DMA row wave)
-#define CFD_TBR_V1 1
-#endif
-#ifndef CFD_TBR_HLD  // K = 4 Jacobi halo wave: its global loads at the step's start (0), after its phase-W
-#define CFD_TBR_HLD 2  // stores (1) or after the first barrier (2); see tbr_halo_wave
-#endif
-#ifndef CFD_TBR_T1D  // K = 4 Jacobi: two T_1 buffers, level 1 stored in phase R -- measured slower, off
-#define CFD_TBR_T1D 0  // (see jacobi3d_tbr)
-#endif
-#ifndef CFD_TBR_T1D_LATE  // T1D: that store after the row's level K (1) or right after its level 1 (0)
-#define CFD_TBR_T1D_LATE 1
-#endif
-
 
 __device__ inline float4 ldb4(__amdgpu_buffer_rsrc_t r, uint32_t byte_ofs) {
     const gv4f v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_ofs, 0, 0);
@@ -354,12 +313,9 @@ __device__ inline float4 any4() {
     asm volatile("" : "=v"(v));
     return make_float4(v.x, v.y, v.z, v.w);
 }
-// Jacobi register-queue entry as two 64-bit values (CFD_TBR_Q64): a float4
-// held this way is copied by two v_mov_b64 when its queue shifts, where the
-// float4's four 32-bit components were copied one v_mov_b32 at a time
-#ifndef CFD_TBR_Q64
-#define CFD_TBR_Q64 1
-#endif
+// Jacobi register-queue entry as two 64-bit values: a float4 held this way
+// is copied by two v_mov_b64 when its queue shifts, where the float4's four
+// 32-bit components were copied one v_mov_b32 at a time
 struct Q4 {
     unsigned long long lo, hi;
 };
@@ -371,7 +327,6 @@ __device__ inline float4 f4_of(const Q4 &q) {
     const v2f_t a = __builtin_bit_cast(v2f_t, q.lo), b = __builtin_bit_cast(v2f_t, q.hi);
     return make_float4(a.x, a.y, b.x, b.y);
 }
-[[maybe_unused]] __device__ inline float4 f4_of(float4 f) { return f; }
 __device__ inline const P4 &f4_of(const P4 &p) { return p; }
 // from LDS: two ds_read2_b32 (words 0, 2 and 1, 3) straight into the pairs
 __device__ inline P4 ldsp(const float *p) { return P4{v2f_t{p[0], p[2]}, v2f_t{p[1], p[3]}}; }
@@ -391,6 +346,23 @@ __device__ inline void sts4s(float *row, int lane, const P4 &v) {
 }
 // pair-tile row (PT): left chunk pair | 64 lanes x pair | right chunk pair
 constexpr int kPairRow = 132;
+// plain tile row: 4 halo | 256 | 4 halo floats
+constexpr int kTileRow = 264;
+// The level tiles' layout in LDS: the first float of tile T_l of a tile of NR
+// level-0 rows.  Level m keeps rows [m, NR - m), of kPairRow floats in a pair
+// tile (PT, m >= 1); T0S: level 0 is a DMA slot and the tiles start at T_1.
+// l = K: the floats of all tiles.  (A loop over every level with the test
+// inside, and the shape as template arguments: the form the kernels' T had;
+// as plain arguments, or with the loop ending at l, the K = 4 kernels'
+// schedules changed.)
+template <int K, int NR, bool PT, bool T0S>
+constexpr int tbr_tile_ofs(int l) {
+    int t = 0;
+#pragma unroll
+    for (int m = T0S ? 1 : 0; m < K; ++m)
+        if (m < l) t += (NR - 2 * m) * (PT && m ? kPairRow : kTileRow);
+    return t;
+}
 __device__ inline v2f_t lds2s(const float *row, int lane, int h) {
     return *reinterpret_cast<const v2f_t *>(row + 4 + 128 * h + 2 * lane);
 }
@@ -446,27 +418,17 @@ __device__ inline v2f_t level2(v2f_t C, v2f_t O, float wl, float er, v2f_t N, v2
 // The halo wave of jacobi3d_tbr (see there): loads the two outermost level-0
 // rows and the 4-float x-halo chunks of every row, and computes levels
 // 1..K-1 of the chunks, in lock step (two barriers per step) with the row waves.
-template <int K, int NWR, int RPW, bool PRE, int PD, int MODE, int F, bool SPLIT, bool PT, bool T0S = false,
-          bool T1D = false>
+template <int K, int NWR, int RPW, bool PRE, int PD, int MODE, int F, bool SPLIT, bool PT, bool T0S = false>
 __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int z0, int z1, int y0, int xs,
-                                              int zl, float *slots = nullptr, float *t1b = nullptr) {
+                                              int zl, float *slots = nullptr) {
     constexpr int NR = NWR * RPW + 2;
-    constexpr int RS = 264, RS2 = kPairRow;
+    constexpr int RS = kTileRow, RS2 = kPairRow;
     // T0S: level 0 of plane z is slot (z - zs) mod 3 of `slots` (the row
     // waves' LDS-DMA staging ring), the level tiles 1..K-1 start at smem
     int t0 = 0;  // this step's slot offset (floats)
-    // T1D: tile T_1 is the one of its two buffers (smem's, t1b) that this
-    // step's phase R reads, buffer (z - zs) & 1 -- the halo wave stores its
-    // level-1 chunks there in phase W and reads level 1 there in phase R
-    float *t1 = smem;
     auto T = [&](int l, int r) -> float * {
         if (T0S && l == 0) return slots + t0 + r * RS;
-        if (T1D && l == 1) return t1 + (r - 1) * RS;
-        int base = 0;
-#pragma unroll
-        for (int m = T0S ? 1 : 0; m < K; ++m)
-            if (m < l) base += (NR - 2 * m) * (PT && m ? RS2 : RS);
-        return smem + base + (r - l) * (PT && l ? RS2 : RS);
+        return smem + tbr_tile_ofs<K, NR, PT, T0S>(l) + (r - l) * (PT && l ? RS2 : RS);
     };
     const int nz = a.nz, ny = a.ny, nx = a.nx;
     const int lane = threadIdx.x & 63;
@@ -524,14 +486,14 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
     const int hw = threadIdx.x >> 6;
     for (int z = zs; z <= zl; ++z) {
         if constexpr (T0S) t0 = ((z - zs) % 3) * (NR * RS);
-        if constexpr (T1D) t1 = ((z - zs) & 1) ? t1b : smem;
         trace_mark(a.trace, hw, z - zs, 0);
         // the step's global loads (nothing reads them before the queues shift
-        // at the end of the step).  HLD (K = 4 Jacobi, T0S): after the first
-        // barrier, so that the phase-W stores below do not stand behind them
-        // -- 1024^3 A/B against loads at the step's start: 1760 -> 1801
-        // Gcell/s (after the phase-W stores, before the barrier: +0.6 %)
-        constexpr int HLD = T0S && K == 4 ? CFD_TBR_HLD : 0;
+        // at the end of the step): at the step's start (HLD = 0), or (HLD = 2:
+        // K = 4 Jacobi, T0S) after the first barrier, so that the phase-W
+        // stores below do not stand behind them -- 1024^3 A/B against loads at
+        // the step's start: 1760 -> 1801 Gcell/s (after the phase-W stores,
+        // before the barrier: +0.6 %)
+        constexpr int HLD = T0S && K == 4 ? 2 : 0;
         auto loads = [&] {
             Lq[PD - 1] = ldlo(z + PD);
             Uq[PD - 1] = ldhi(z + PD);
@@ -560,7 +522,6 @@ __device__ __forceinline__ void tbr_halo_wave(const TbrArgs a, float *smem, int 
                     }
                 }
         }
-        if constexpr (HLD == 1) loads();
         trace_mark(a.trace, hw, z - zs, 1);
         __syncthreads();
         trace_mark(a.trace, hw, z - zs, 2);
@@ -646,7 +607,7 @@ template <int K, int NWR, int RPW, bool PRE, int PD, int MODE, int F = 0, bool S
 __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     constexpr int NR = NWR * RPW + 2;  // level-0 rows per tile
     constexpr int W = NR - 2 * K;      // output rows
-    constexpr int RS = 264;            // LDS row: 4 halo | 256 | 4 halo floats
+    constexpr int RS = kTileRow;       // LDS row: 4 halo | 256 | 4 halo floats
     static_assert(K >= 1 && K <= 4 && W >= 1, "bad shape");
     static_assert(2 * NR <= 64, "halo wave: one lane per (row, side)");
     // PT (red-black GS on the LDS-DMA path): the tiles of levels 1..K-1 hold
@@ -664,41 +625,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     // phase W no longer copies level 0 into a tile: a quarter of the K = 4
     // pass's LDS stores, the slow direction of the LDS (ds_write_b128 ~79
     // B/clk/CU against 256 for reads)
-    constexpr bool T0S = MODE == kJacobi && PD == 1 && CFD_TBR_LB && CFD_TBR_T0S;
+    constexpr bool T0S = MODE == kJacobi && PD == 1;
     constexpr int SLOT = NR * RS;
-    constexpr int TOTAL = [] {
-        int t = 0;
-        for (int l = T0S ? 1 : 0; l < K; ++l) t += (NR - 2 * l) * (PT && l ? RS2 : RS);
-        return t;
-    }();
+    constexpr int TOTAL = tbr_tile_ofs<K, NR, PT, T0S>(K);
     __shared__ __attribute__((aligned(16))) float smem[TOTAL > 0 ? TOTAL : 4];
     __shared__ __attribute__((aligned(16))) float slots[T0S ? 3 * SLOT : 4];
-    // T1D (the K = 4 Jacobi at 2 rows per wave on T0S, where LDS has room for
-    // it): a second buffer for T_1, the largest level tile.  Step z (parity
-    // b = (z - zs) & 1, a run-time scalar formed the same way by both wave
-    // kinds) reads level 1 of plane z - 1 from buffer b -- smem's T_1 when
-    // b = 0, t1b when b = 1 -- and the row waves store level 1 of plane z into
-    // buffer 1 - b in phase R (right after computing it, or after the row's
-    // level K: CFD_TBR_T1D_LATE), so phase W has a third fewer ds_write_b128
-    // (22 of 66 per step) in front of its barrier.  No barrier is added: buffer 1 - b was last read in phase R of
-    // step z - 1 (it held plane z - 2) and is next read in phase R of step
-    // z + 1: step z - 1's end-of-step barrier (and step z's phase-W barrier)
-    // lie before this step's stores, step z's end-of-step barrier (and step
-    // z + 1's phase-W barrier) after them.
-    // The halo wave keeps its timing (its level-1 chunks go into buffer b in
-    // phase W of step z, columns the row waves never write).
-    // The phase-R store is not predicated on xin: a branch there splits the
-    // level loop's one basic block (-1 %); a lane beyond nx stores its
-    // never-used value into its own columns, which only such lanes read.
-    // Measured (1024^3, Gcell/s, parent 1766-1771): store right after the
-    // level-1 update 1714 with the predicate, 1730 without; after the row's
-    // level K (CFD_TBR_T1D_LATE) 1735 / 1746.  Phase W was not bound by the
-    // row waves' stores but by the halo wave (see the file header), and the
-    // stores cost phase R more than they saved: off by default.
-    constexpr bool T1D = T0S && K == 4 && RPW == 2 && CFD_TBR_T1D &&
-                         (TOTAL + 3 * SLOT + (NR - 2) * RS) * 4 <= 160 * 1024;
-    constexpr int T1N = (NR - 2) * RS;  // floats of T_1
-    __shared__ __attribute__((aligned(16))) float t1b[T1D ? T1N : 4];
     // DMA staging (row waves, when it fits in LDS with the level tiles): the
     // level-0 row of plane z + 2 and the rhs row of plane z + 1 are fetched by
     // LDS-DMA at the start of step z into the even/odd buffers and read at
@@ -719,17 +650,13 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     // EARLY (DMA path): each step's staging rows are fetched two steps ahead,
     // in phase R right after the wave read its rows of the same buffer,
     // instead of one step ahead at the start of phase W
-    constexpr bool EARLY = DMA && MODE == kRbgs && CFD_TBR_EARLY;
+    constexpr bool EARLY = DMA && MODE == kRbgs;
     constexpr int SST = DMA && !T0S ? SR_ * 256 : 4;
     constexpr int SSR = RDMA ? SR_ * 256 : 4;
     __shared__ __attribute__((aligned(16))) float st_p0[SST], st_p1[SST], st_r0[SSR], st_r1[SSR];
     // level l keeps rows [l, NR - l) (T0S: l >= 1 only; level 0 is a slot)
     auto T = [&](int l, int r) -> float * {
-        int base = 0;
-#pragma unroll
-        for (int m = T0S ? 1 : 0; m < K; ++m)
-            if (m < l) base += (NR - 2 * m) * (PT && m ? RS2 : RS);
-        return smem + base + (r - l) * (PT && l ? RS2 : RS);
+        return smem + tbr_tile_ofs<K, NR, PT, T0S>(l) + (r - l) * (PT && l ? RS2 : RS);
     };
 
     static_assert(!PT || DMA, "pair tiles: LDS-DMA path");
@@ -821,9 +748,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     // unrolled by 3, not 6: V and the level queues take compile-time slots
     // (72 of the 96 v_mov_b64 per two steps gone), Rq keeps shifting, and the
     // loop body is half the 6-step one that spilled.  It fits 168 VGPRs
-    // without scratch only with V1 and any4() (see the DMA row wave): 159.
+    // without scratch only with level 0 left in the slot ring and any4() (see
+    // the DMA row wave): 159.
     // r07, 1024^3: VALU per step and full-work wave 301 -> 243, pass -2 %.
-    constexpr bool ROT3 = T0S && K == 4 && RPW == 2 && !RDMA && !SHIFTQ && CFD_TBR_ROT3;
+    constexpr bool ROT3 = T0S && K == 4 && RPW == 2 && !RDMA && !SHIFTQ;
     constexpr bool ROT = (DMA && K <= 3 && (MODE == kJacobi || RPW <= 2) && !SHIFTQ) || ROT3;
     // (a K = 4 Jacobi with its rhs queue rotated with period 4 -- a march
     // unrolled by 4 -- spilled 22 VGPRs and took 4.96-5.04 ms per pass against
@@ -848,13 +776,6 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
         if constexpr (MODE == kRbgs) chgl[slot(l)] = fmaxf(chgl[slot(l)], lm);
     };
 
-    if constexpr (T1D) {
-        // step zs reads buffer 0 before any phase R stored into it: zeros, the
-        // empty level-1 queues' value that phase W used to store there (the
-        // pipeline fill computes from them; nothing of it reaches an output)
-        for (int k = threadIdx.x; k < T1N / 4; k += blockDim.x) sts4(smem + 4 * k, z4);
-        if constexpr (!ZERO) __syncthreads();
-    }
     if constexpr (T0S && ZERO) {
         // level 0 = 0 (no DMA fills the slots): zero them once
         for (int k = threadIdx.x; k < 3 * SLOT / 4; k += blockDim.x) sts4(slots + 4 * k, z4);
@@ -863,6 +784,15 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
     if (wv < NWR) {
         if constexpr (DMA) {
             // --------------------------------------------- row wave, DMA-staged
+            // Two forms of it, and nothing between them.  Jacobi: lane-based
+            // LDS addressing (LB) on the slot ring (T0S), exact vmcnt waits
+            // with the DMAs issued one step ahead (XW).  Red-black GS: generic
+            // tile pointers, staging buffers, DMAs two steps ahead (EARLY).
+            // Both carry the per-step scalar state by additions (see sd_in).
+            constexpr bool LB = MODE == kJacobi;
+            constexpr bool XW = MODE == kJacobi && !EARLY;
+            static_assert(LB == T0S, "DMA row wave: lane-based addressing is written for the slot ring only");
+            static_assert(XW != EARLY, "DMA row wave: exactly one of the two fetch schedules (and vmcnt waits)");
             int rr[RPW];
             uint32_t bo[RPW], so[RPW];  // load / store byte offsets in a plane, kOob outside
             bool irow[RPW], orow[RPW];
@@ -893,48 +823,33 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             // cells keep the previous level's values, which the level below
             // holds): half the registers of the level queues
             using QT = std::conditional_t<MODE == kRbgs, v2f_t, float4>;
-            // Jacobi queue entries: Q4 (64-bit halves) or float4
-            using JQ = std::conditional_t<CFD_TBR_Q64 != 0, Q4, float4>;
-            // GS: V and Rq hold colour pairs (P4)
-            using VT = std::conditional_t<MODE == kRbgs, P4, JQ>;
-            using QQ = std::conditional_t<MODE == kRbgs, v2f_t, JQ>;
+            // Jacobi: queue entries are Q4 (64-bit halves); GS: V and Rq hold
+            // colour pairs (P4)
+            using VT = std::conditional_t<MODE == kRbgs, P4, Q4>;
+            using QQ = std::conditional_t<MODE == kRbgs, v2f_t, Q4>;
             auto toV = [](float4 f) -> VT {
                 if constexpr (MODE == kRbgs)
                     return split4(f);
-                else if constexpr (CFD_TBR_Q64 != 0)
-                    return q4_of(f);
                 else
-                    return f;
+                    return q4_of(f);
             };
-            // V1 (ROT3): level 1 takes its own row of planes z and z + 1 from
-            // the slots they sit in (one more ds_read_b128 per row and step) and
+            // ROT3: level 1 takes its own row of planes z and z + 1 from the
+            // slots they sit in (one more ds_read_b128 per row and step) and
             // only plane z - 1 is carried, in V[j][0]: 16 VGPRs fewer, which is
             // what lets the rotated queues fit without scratch
-            constexpr bool V1 = ROT3 && CFD_TBR_V1;
             VT V[RPW][3], Rq[RPW][K];
             QQ Q[RPW][K][3];
             float4 Rn[RPW];  // !RDMA: the rhs row of the next step's plane, in flight
-            // Lane-based LDS addressing (Jacobi): every tile and staging access
+            // Lane-based LDS addressing (LB, Jacobi): every tile and slot access
             // of a row wave is one of a few per-wave base addresses (the lane's
-            // float4 in the wave's first row; the level tiles past T_1 from a
-            // second base, so offsets fit the 16-bit immediate) plus a
-            // compile-time offset, folded into the DS instruction.  The bases
-            // are made opaque once per step, so the compiler keeps 4 + 2 VGPRs
-            // instead of hoisting one address per (level, row) out of the
-            // z-loop -- which spilled 5 VGPRs at K = 4 whose scratch reloads
-            // each waited vmcnt(0), i.e. for the DMAs of the next planes.
-            constexpr bool LB = MODE == kJacobi && CFD_TBR_LB;
-            // (T0S: tiles 1..K-1 all within the 16-bit offset of one base)
-            constexpr int kTb2 = [] {  // first float of tile T_2 (0 when K < 3)
-                int t = 0;
-                for (int m = 0; m < 2 && m < K; ++m) t += (NR - 2 * m) * RS;
-                return K >= 3 && !T0S ? t : 0;
-            }();
-            auto tbase = [](int l) {
-                int t = 0;
-                for (int m = T0S ? 1 : 0; m < l; ++m) t += (NR - 2 * m) * RS;
-                return t;
-            };
+            // float4 in the wave's first row; the tiles 1..K-1 all lie within
+            // the 16-bit offset of one base) plus a compile-time offset, folded
+            // into the DS instruction.  The bases are made opaque once per
+            // step, so the compiler keeps 5 VGPRs instead of hoisting one
+            // address per (level, row) out of the z-loop -- which spilled 5
+            // VGPRs at K = 4 whose scratch reloads each waited vmcnt(0), i.e.
+            // for the DMAs of the next planes.
+            auto tbase = [](int l) { return tbr_tile_ofs<K, NR, PT, T0S>(l); };
             [[maybe_unused]] const GsPk gk = MODE == kRbgs ? gs_pk(a) : GsPk{};
             const uint32_t lds_st_p0 = lds_addr(st_p0), lds_st_p1 = lds_addr(st_p1);
             const uint32_t lds_st_r0 = lds_addr(st_r0), lds_st_r1 = lds_addr(st_r1);
@@ -944,14 +859,9 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             (void)lds_st_r1;
             const uint32_t lbA0 = lds_addr(smem) + 4u * (uint32_t)(wv * RS + 4 + 4 * lane);
             const uint32_t lbU0 = lds_addr(smem) + 4u * (uint32_t)(wv * RS);
-            const uint32_t lbP00 = lds_addr(st_p0) + 4u * (uint32_t)(wv * 256 + 4 * lane);
-            const uint32_t lbP10 = lds_addr(st_p1) + 4u * (uint32_t)(wv * 256 + 4 * lane);
-            // T0S: the lane's float4 in row wv of slot 0, and row wv's first float
+            // the lane's float4 in row wv of slot 0, and row wv's first float
             const uint32_t lbS0 = lds_addr(slots) + 4u * (uint32_t)(wv * RS + 4 + 4 * lane);
             const uint32_t lbUS0 = lds_addr(slots) + 4u * (uint32_t)(wv * RS);
-            // T1D: byte distance from T_1's first buffer (smem's) to the second
-            [[maybe_unused]] uint32_t t1dist = 0;
-            if constexpr (T1D) t1dist = lds_addr(t1b) - lds_addr(smem);
             // a row's DMA destination in slot q: row rr[j], column 4
             auto slot_row = [&](int q, int j) { return slots + q * SLOT + rr[j] * RS + 4; };
 #pragma unroll
@@ -960,8 +870,8 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 for (int l = 0; l < K; ++l) Q[j][l][0] = Q[j][l][1] = Q[j][l][2] = QQ{};
                 // planes zs - 1 and zs in slots 2 and 0 (slot (q - zs) mod 3), or 0
                 // and 1 (shifted queues)
-                V[j][V1 ? 0 : ROT ? 2 : 0] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs - 1, nz, plane), bo[j]));
-                if constexpr (!V1) {
+                V[j][ROT3 ? 0 : ROT ? 2 : 0] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs - 1, nz, plane), bo[j]));
+                if constexpr (!ROT3) {
                     V[j][ROT ? 0 : 1] = toV(ZERO ? z4 : ldb4(plane_rsrc(a.in, zs, nz, plane), bo[j]));
                     V[j][ROT ? 1 : 2] = toV(z4);
                 }
@@ -998,7 +908,6 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             // waits the compiler places for them in the loop's first step are
             // no-ops (it does not count the LDS-DMAs, so a wait of its own for
             // an older load would wait for this step's DMAs as well)
-            constexpr bool XW = MODE == kJacobi && !EARLY && CFD_TBR_XW;
             if constexpr (XW) wait_vmcnt<0>();
             // Register queues without moves: plane q of level 0 / level l lives
             // in slot (q - zs) mod 3 of V / Q[.][l], and (when the unroll
@@ -1012,17 +921,16 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
             constexpr int kND = ((ZERO ? 0 : 1) + (RDMA ? 1 : 0)) * RPW, kNR = RDMA ? 0 : RPW, kNSK = RPW,
                           kNSR = RHSW ? RPW : 0;
             static_assert(2 * kNSK + 2 * kNR + kNSR + kND < 64, "vmcnt range");
-            // SD (Jacobi, XW): the per-step scalar state -- the plane bases of
-            // the DMA source (in, plane z + 2), the rhs loads (div, z + 1), the
-            // level-K stores (out, z - K + 1) and the first pass's rhs stores
-            // (rhs_out, z), and the slot ring's byte offsets -- carried from
-            // step to step by additions and rotations.  Recomputed per step
-            // they were ~80 SALU per wave in phase W (64-bit products, a
-            // division by 3), and the CU's one scalar unit serialised the 12
-            // waves' phase W (r05 trace: the third wave of each SIMD reached
-            // the first barrier ~1150 cycles after the first)
+            // The per-step scalar state -- the plane bases of the DMA source
+            // (in, plane z + 2), the rhs loads (div, z + 1), the level-K stores
+            // (out, z - K + 1) and the first pass's rhs stores (rhs_out, z), and
+            // the slot ring's byte offsets -- is carried from step to step by
+            // additions and rotations.  Recomputed per step (plane_rsrc4, a slot
+            // index (z - zs) mod 3) it was ~80 SALU per wave in phase W (64-bit
+            // products, a division by 3), and the CU's one scalar unit
+            // serialised the 12 waves' phase W (r05 trace: the third wave of
+            // each SIMD reached the first barrier ~1150 cycles after the first)
             // (the red-black GS's EARLY path too: its DMAs fetch planes z + 3 / rhs z + 2)
-            constexpr bool SD = (XW || EARLY) && CFD_TBR_SD;
             constexpr int kAh = EARLY ? 3 : 2;  // plane of the step's phi DMA, relative to z
             const uint64_t pbytes = (uint64_t)plane * sizeof(float);
             uint64_t sd_in = (uint64_t)(uintptr_t)a.in + (uint64_t)(int64_t)(zs + kAh) * pbytes;
@@ -1045,8 +953,6 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)b, (short)0, ok ? (int)pbytes : 0,
                                                          0x00020000);
             };
-            (void)rsrc4;
-            (void)rsrc;
             auto step = [&](int z, auto parc, auto rotc, auto bpc) {
                 constexpr int E = decltype(parc)::value;  // (z - zs) & 1
                 constexpr int R = decltype(rotc)::value;  // (z - zs) mod 6 (ROT), else 0
@@ -1063,56 +969,37 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 // its tests (one per row and cell of the step's colour, shared
                 // by the levels) live in SGPRs for one step; hoisted out of the
                 // march they are 8 SGPR pairs across it
-                if constexpr (MSK && CFD_TBR_MSTEP) asm volatile("" : "+v"(mk));
-                float *const pw = E ? st_p1 : st_p0;
+                if constexpr (MSK) asm volatile("" : "+v"(mk));
                 float *const rw = E ? st_r1 : st_r0;
                 const float *const pr = E ? st_p0 : st_p1;
                 const float *const rdr = E ? st_r0 : st_r1;
                 // LB: this step's opaque bases; tp(l, d): the lane's float4 of
                 // level tile l in row rr[j] + d (d = j * NWR + delta); up(l, d):
-                // that row's first float (uniform)
-                // T0S: slot sz holds plane z (this step's level 0), sn plane
-                // z + 1 (landed), sd receives plane z + 2
-                const int sz = T0S && !SD ? (z - zs) % 3 : 0;
-                const int sn = sz == 2 ? 0 : sz + 1, sd = sn == 2 ? 0 : sn + 1;
-                // byte offsets of the slots of planes z, z + 1, z + 2
-                const uint32_t oz = SD ? (uint32_t)sd_oz : 4u * (uint32_t)(sz * SLOT);
-                const uint32_t on = SD ? (uint32_t)sd_on : 4u * (uint32_t)(sn * SLOT);
-                const uint32_t od = SD ? (uint32_t)sd_od : 4u * (uint32_t)(sd * SLOT);
-                uint32_t bA = lbA0, bU = lbU0, bP = E ? lbP00 : lbP10;
+                // that row's first float (uniform).  Level 0 is the slot of
+                // plane z (bases bS / bUS); bSn: the slot of plane z + 1 (landed).
+                // oz, on, od: byte offsets of the slots of planes z, z + 1 and
+                // z + 2 (which receives this step's DMA)
+                const uint32_t oz = (uint32_t)sd_oz, on = (uint32_t)sd_on, od = (uint32_t)sd_od;
+                uint32_t bA = lbA0, bU = lbU0;
                 uint32_t bS = lbS0 + oz, bSn = lbS0 + on;
                 uint32_t bUS = lbUS0 + oz;
-                if constexpr (LB && T0S)
-                    asm volatile("" : "+v"(bA), "+v"(bU), "+v"(bS), "+v"(bSn), "+v"(bUS));
-                else if constexpr (LB)
-                    asm volatile("" : "+v"(bA), "+v"(bU), "+v"(bP));
-                const uint32_t bB = bA + 4u * kTb2, bUB = bU + 4u * kTb2;
-                // T1D: T_1 is read in the buffer of this step's parity (bR1,
-                // bUR1) and level 1 stored into the other (bW1); the second
-                // buffer lies beyond the 16-bit offset of bA, so these are
-                // bases of their own, opaque per step like the others
-                [[maybe_unused]] uint32_t bR1 = 0, bUR1 = 0, bW1 = 0;
-                if constexpr (T1D) {
-                    const bool odd = ((z - zs) & 1) != 0;
-                    const uint32_t t1r = odd ? t1dist : 0u, t1w = odd ? 0u : t1dist;
-                    bR1 = lbA0 + t1r;
-                    bUR1 = lbU0 + t1r;
-                    bW1 = lbA0 + t1w;
-                    asm volatile("" : "+v"(bR1), "+v"(bUR1), "+v"(bW1));
-                }
+                if constexpr (LB) asm volatile("" : "+v"(bA), "+v"(bU), "+v"(bS), "+v"(bSn), "+v"(bUS));
+                // (Off the slot ring the tiles from T_2 on took a second base, for
+                // the 16-bit offset.  Here both are one address, but the choice
+                // between two names stays: written with bA / bU alone, the N and
+                // S reads of 16 Jacobi kernels, all K = 4 ones among them, are
+                // scheduled in another order.)
+                const uint32_t bB = bA, bUB = bU;
                 auto tp = [&](int l, int d) -> lfloat * {
-                    if (T0S && l == 0) return lds_ptr(bS) + (1 + d) * RS;
-                    if (T1D && l == 1) return lds_ptr(bR1) + (tbase(1) + d * RS);
+                    if (l == 0) return lds_ptr(bS) + (1 + d) * RS;
                     return l < 2 ? lds_ptr(bA) + (tbase(l) + (1 + d - l) * RS)
-                                 : lds_ptr(bB) + (tbase(l) - kTb2 + (1 + d - l) * RS);
+                                 : lds_ptr(bB) + (tbase(l) + (1 + d - l) * RS);
                 };
                 auto up = [&](int l, int d) -> const lfloat * {
-                    if (T0S && l == 0) return lds_ptr(bUS) + (1 + d) * RS;
-                    if (T1D && l == 1) return lds_ptr(bUR1) + (tbase(1) + d * RS);
+                    if (l == 0) return lds_ptr(bUS) + (1 + d) * RS;
                     return l < 2 ? lds_ptr(bU) + (tbase(l) + (1 + d - l) * RS)
-                                 : lds_ptr(bUB) + (tbase(l) - kTb2 + (1 + d - l) * RS);
+                                 : lds_ptr(bUB) + (tbase(l) + (1 + d - l) * RS);
                 };
-                (void)sd;
                 (void)tp;
                 (void)up;
                 // !RDMA: this step's rhs row (loaded last step) and the next one's load
@@ -1122,26 +1009,22 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                     for (int j = 0; j < RPW; ++j) Rc[j] = Rn[j];  // landed: see phase R
                 }
                 if constexpr (!EARLY) {
-                    const v4i32 rp = SD ? rsrc4(sd_in, z + 2 >= 0 && z + 2 <= nz - 1) : plane_rsrc4(a.in, z + 2, nz, plane);
-                    const v4i32 rd = SD ? rsrc4(sd_div, z + 1 >= 0 && z + 1 <= nz - 1) : plane_rsrc4(a.div, z + 1, nz, plane);
+                    // (Jacobi, so T0S: plane z + 2 into the slot at sd_od)
+                    const v4i32 rp = rsrc4(sd_in, z + 2 >= 0 && z + 2 <= nz - 1);
+                    const v4i32 rd = rsrc4(sd_div, z + 1 >= 0 && z + 1 <= nz - 1);
 #pragma unroll
                     for (int j = 0; j < RPW; ++j) {
-                        if (!ZERO)
-                            dma_row(rp, bo[j],
-                                    T0S ? (SD ? (float *)((char *)slots + od) + rr[j] * RS + 4 : slot_row(sd, j))
-                                        : pw + (rr[j] - 1) * 256);
+                        if (!ZERO) dma_row(rp, bo[j], (float *)((char *)slots + od) + rr[j] * RS + 4);
                         if constexpr (RDMA) dma_row(rd, bo[j], rw + (rr[j] - 1) * 256);
                     }
                 } else {
-                    (void)pw;
                     (void)rw;
                 }
                 if constexpr (!RDMA) {
                     (void)rw;
                     (void)rdr;
                     const __amdgpu_buffer_rsrc_t rdn =
-                        SD ? rsrc(sd_div - (EARLY ? pbytes : 0), z + 1 >= 0 && z + 1 <= nz - 1)  // (sd_div: rhs z + kAh - 1)
-                           : plane_rsrc(a.div, z + 1, nz, plane);
+                        rsrc(sd_div - (EARLY ? pbytes : 0), z + 1 >= 0 && z + 1 <= nz - 1);  // (sd_div: rhs z + kAh - 1)
 #pragma unroll
                     for (int j = 0; j < RPW; ++j) {
                         if constexpr (!XW) Rc[j] = Rn[j];
@@ -1151,19 +1034,12 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 // phase W: level 0 of plane z and level l of plane z - l
 #pragma unroll
                 for (int j = 0; j < RPW; ++j) {
-                    if (xin && !T0S) {  // (T0S: level 0 is in its slot already)
-                        if constexpr (SPLIT)
-                            sts4s(T(0, rr[j]), lane, f4_of(V[j][vs(0)]));
-                        else if constexpr (LB)
-                            sts4l(tp(0, j * NWR), f4_of(V[j][vs(0)]));
-                        else
-                            sts4(T(0, rr[j]) + 4 + 4 * lane, f4_of(V[j][vs(0)]));
+                    if constexpr (SPLIT) {  // (Jacobi, T0S: level 0 is in its slot already)
+                        if (xin) sts4s(T(0, rr[j]), lane, f4_of(V[j][vs(0)]));
                     }
 #pragma unroll
                     for (int l = 1; l < K; ++l)
-                        if (T1D && l == 1) {
-                            // (stored in phase R of the step that computed it)
-                        } else if (xin && rr[j] >= l && rr[j] < NR - l) {
+                        if (xin && rr[j] >= l && rr[j] < NR - l) {
                             if constexpr (MODE == kRbgs) {
                                 // level l of plane z - l: its own pair (computed last
                                 // step, at 1 - h) joined with level l - 1's (two steps
@@ -1176,16 +1052,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                     *reinterpret_cast<v2f_t *>(T(l, rr[j]) + 2 + 2 * lane) =
                                         Q[j][l][ROT ? sl3(R - l) : 2];
                                 } else {
-                                    const float4 f = join2(lo, Q[j][l][ROT ? sl3(R - l) : 2], h);
-                                    if constexpr (SPLIT)
-                                        sts4s(T(l, rr[j]), lane, f);
-                                    else
-                                        sts4(T(l, rr[j]) + 4 + 4 * lane, f);
+                                    sts4s(T(l, rr[j]), lane, join2(lo, Q[j][l][ROT ? sl3(R - l) : 2], h));
                                 }
-                            } else if constexpr (LB) {
-                                sts4l(tp(l, j * NWR), f4_of(Q[j][l][ROT ? sl3(R - l) : 2]));
                             } else {
-                                sts4(T(l, rr[j]) + 4 + 4 * lane, f4_of(Q[j][l][ROT ? sl3(R - l) : 2]));
+                                sts4l(tp(l, j * NWR), f4_of(Q[j][l][ROT ? sl3(R - l) : 2]));
                             }
                         }
                 }
@@ -1198,14 +1068,12 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 // pass) and DMAs, and step z - 1's level-K stores
                 if constexpr (EARLY)
                     wait_vmcnt<2 * kNSK + 2 * kNR + kNSR + kND>();
-                else if constexpr (XW)
-                    // issued after step z - 1's DMAs: its rhs loads, rhs
+                else
+                    // (XW) issued after step z - 1's DMAs: its rhs loads, rhs
                     // stores (first pass), 0..RPW level-K stores, and this
                     // step's DMAs and rhs loads -- so last step's level-K
                     // stores may still be in flight
                     wait_vmcnt<2 * kNR + kNSR + kND>();
-                else
-                    wait_vmcnt<((ZERO ? 0 : 1) + 1) * RPW>();
                 trace_mark(a.trace, wv, z - zs, 1);
                 lds_barrier();
                 trace_mark(a.trace, wv, z - zs, 2);
@@ -1213,14 +1081,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 for (int j = 0; j < RPW; ++j) {
                     if constexpr (MODE == kRbgs)
                         V[j][vs(1)] = ldsp(pr + (rr[j] - 1) * 256 + 4 * lane);
-                    else if constexpr (V1)
+                    else if constexpr (ROT3)
                         ;  // (read where level 1 uses it)
-                    else if constexpr (LB && T0S)
-                        V[j][vs(1)] = toV(ZERO ? z4 : lds4l(lds_ptr(bSn) + (1 + j * NWR) * RS));
-                    else if constexpr (LB)
-                        V[j][vs(1)] = toV(ZERO ? z4 : lds4l(lds_ptr(bP) + j * NWR * 256));
                     else
-                        V[j][vs(1)] = toV(ZERO ? z4 : lds4(pr + (rr[j] - 1) * 256 + 4 * lane));
+                        V[j][vs(1)] = toV(ZERO ? z4 : lds4l(lds_ptr(bSn) + (1 + j * NWR) * RS));
                     constexpr int RS0 = ROTR ? slk(R, K) : 0;  // slot of this step's rhs
                     if constexpr (!ROTR) {
 #pragma unroll
@@ -1241,10 +1105,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                         // the rhs of plane z for the later passes: owned planes and
                         // rows only (so[j] = kOob elsewhere), every x of the row
                         const bool own = z >= z0 && z < z1;
-                        const __amdgpu_buffer_rsrc_t ro =
-                            SD ? rsrc(sd_rhs, own)
-                               : __builtin_amdgcn_make_buffer_rsrc(a.rhs_out + (size_t)(own ? z : 0) * plane, (short)0,
-                                                                   own ? (int)(plane * sizeof(float)) : 0, 0x00020000);
+                        const __amdgpu_buffer_rsrc_t ro = rsrc(sd_rhs, own);
                         const float4 rq = f4_of(Rq[j][RS0]);
                         const gv4f rv = {rq.x, rq.y, rq.z, rq.w};
                         __builtin_amdgcn_raw_buffer_store_b128(rv, ro, (int)so[j], 0, kStoreNt);
@@ -1255,8 +1116,8 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                     // reads are done, fetch step z + 2's rows into them (plane
                     // z + 3, rhs z + 2), two steps ahead and off phase W
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    const v4i32 rp = SD ? rsrc4(sd_in, z + 3 >= 0 && z + 3 <= nz - 1) : plane_rsrc4(a.in, z + 3, nz, plane);
-                    const v4i32 rd = SD ? rsrc4(sd_div, z + 2 >= 0 && z + 2 <= nz - 1) : plane_rsrc4(a.div, z + 2, nz, plane);
+                    const v4i32 rp = rsrc4(sd_in, z + 3 >= 0 && z + 3 <= nz - 1);
+                    const v4i32 rd = rsrc4(sd_div, z + 2 >= 0 && z + 2 <= nz - 1);
                     // destinations as 32-bit LDS addresses (the staging rows'
                     // generic pointers, hoisted out of the march, were 64-bit
                     // SGPR pairs with a null-check select each: r05's in-loop
@@ -1279,10 +1140,10 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                     float wl, er;  // the x-halo cells xs - 1, xs + 256
                 };
                 auto fetch = [&](int l, int j) {
-                    const int r = rr[j];
                     LdsIn o;
-                    const float *row = T(l - 1, r);
                     if constexpr (MODE == kRbgs) {
+                        const int r = rr[j];
+                        const float *row = T(l - 1, r);
                         const int h = (BPv ^ E ^ (j * NWR)) & 1;
                         // cell xs - 1 (the left chunk's cell 3) and xs + 256 (the
                         // right chunk's cell 0), level l - 1; in a pair tile the
@@ -1294,15 +1155,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                         if (pt) {
                             o.N = *reinterpret_cast<const v2f_t *>(T(l - 1, r + 1) + 2 + 2 * lane);
                             o.S = *reinterpret_cast<const v2f_t *>(T(l - 1, r - 1) + 2 + 2 * lane);
-                        } else if (SPLIT) {
+                        } else {  // (SPLIT)
                             o.N = lds2s(T(l - 1, r + 1), lane, h);
                             o.S = lds2s(T(l - 1, r - 1), lane, h);
-                        } else {
-                            o.N = pick2(lds4(T(l - 1, r + 1) + 4 + 4 * lane), h);
-                            o.S = pick2(lds4(T(l - 1, r - 1) + 4 + 4 * lane), h);
                         }
-                    } else if constexpr (LB) {
-                        (void)row;
+                    } else {  // (LB)
                         o.wl = up(l - 1, j * NWR)[3];
                         o.er = up(l - 1, j * NWR)[260];
                         o.N = lds4l(tp(l - 1, j * NWR + 1));
@@ -1312,19 +1169,19 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                         // update.  Pinned up here with the x-halo reads, one round
                         // trip: 1756.5 against 1754.7 Gcell/s at 1024^3, inside the
                         // runs' spread -- r07, not kept)
-                    } else {
-                        o.wl = row[3];
-                        o.er = row[260];
-                        o.N = lds4(T(l - 1, r + 1) + 4 + 4 * lane);
-                        o.S = lds4(T(l - 1, r - 1) + 4 + 4 * lane);
                     }
                     return o;
                 };
 #pragma unroll
                 for (int l = 1; l <= K; ++l) {
                     const int p = z - l + 1;
-                    // (SD: two compares against the fixed planes found once per launch)
-                    const bool fx = SD ? ((p == sd_flo) | (p == sd_fhi)) : fixedp(p);
+                    // (two compares against the fixed planes found once per launch)
+                    const bool fx = (p == sd_flo) | (p == sd_fhi);
+                    // (fixedp, the plain row wave's form of this test, stays named
+                    // here: the step captures what its body names, and without
+                    // this capture every GS kernel of this path comes out with
+                    // another register assignment -- the same instructions)
+                    (void)fixedp;
                     if (!RDMA && XW && l == K) {
                         // the next step's rhs rows (loaded at this step's
                         // start) taken into registers here, as late as
@@ -1380,12 +1237,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                 // level K of plane p: this pair at h, level K - 1's at 1 - h
                                 const float4 f = join2(v, Op, h);
                                 const bool own = p >= z0 && p < z1;
-                                const __amdgpu_buffer_rsrc_t ro =
-                                    SD ? rsrc(sd_out, own)
-                                       : __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)(own ? p : 0) * plane,
-                                                                           (short)0,
-                                                                           own ? (int)(plane * sizeof(float)) : 0,
-                                                                           0x00020000);
+                                const __amdgpu_buffer_rsrc_t ro = rsrc(sd_out, own);
                                 const gv4f vv = {f.x, f.y, f.z, f.w};
                                 __builtin_amdgcn_raw_buffer_store_b128(vv, ro, (int)so[j], 0, kStoreNt);
                             }
@@ -1393,7 +1245,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                         } else if ((ROT3 && l == 1) || (r >= l && r < NR - l)) {  // (level 1: every row)
                             // level l-1 at planes p (c), p + 1 (U), p - 1 (D)
                             float4 c, U, D;
-                            if constexpr (V1) {
+                            if constexpr (ROT3) {
                                 if (l == 1) {  // planes z, z + 1 from their slots, z - 1 carried
                                     c = ZERO ? z4 : lds4l(tp(0, j * NWR));
                                     U = ZERO ? z4 : lds4l(lds_ptr(bSn) + (1 + j * NWR) * RS);
@@ -1401,7 +1253,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                     V[j][0] = toV(c);
                                 }
                             }
-                            if (!V1 || l > 1) {
+                            if (!ROT3 || l > 1) {
                                 c = f4_of(l == 1 ? V[j][vs(0)] : Q[j][l - 1][qs(l - 1, 1)]);
                                 U = f4_of(l == 1 ? V[j][vs(1)] : Q[j][l - 1][qs(l - 1, 2)]);
                                 D = f4_of(l == 1 ? V[j][vs(-1)] : Q[j][l - 1][qs(l - 1, 0)]);
@@ -1425,21 +1277,11 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                                     Q[j][l][1] = Q[j][l][2];
                                     Q[j][l][2] = toV(v);
                                 }
-                                // T1D: level 1 of plane z into the T_1 buffer nobody
-                                // reads in this step, for level 2 of the next one
-                                if constexpr (T1D && !CFD_TBR_T1D_LATE) {
-                                    if (l == 1) sts4l(lds_ptr(bW1) + (tbase(1) + j * NWR * RS), v);
-                                }
                             } else {
                                 // unconditional buffer store: rows, lanes and planes this
                                 // tile does not own fall out of range and are dropped
                                 const bool own = p >= z0 && p < z1;
-                                const __amdgpu_buffer_rsrc_t ro =
-                                    SD ? rsrc(sd_out, own)
-                                       : __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)(own ? p : 0) * plane,
-                                                                           (short)0,
-                                                                           own ? (int)(plane * sizeof(float)) : 0,
-                                                                           0x00020000);
+                                const __amdgpu_buffer_rsrc_t ro = rsrc(sd_out, own);
                                 const gv4f vv = {v.x, v.y, v.z, v.w};
                                 __builtin_amdgcn_raw_buffer_store_b128(vv, ro, (int)so[j], 0, kStoreNt);
                             }
@@ -1450,10 +1292,6 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                             // join of the two paths cost the hot one a copy of the old
                             // value before the branch and one of the new value after
                             if (l < K) Q[j][l][sl3(R - l + 1)] = toV(any4());
-                        }
-                        if constexpr (T1D && CFD_TBR_T1D_LATE) {  // (every row, also outside level K's range)
-                            if (l == K)
-                                sts4l(lds_ptr(bW1) + (tbase(1) + j * NWR * RS), f4_of(Q[j][1][ROT ? sl3(R) : 2]));
                         }
                         if (EARLY && l == K && !(r >= l && r < NR - l)) {
                             // a row outside level K's range still issues its store
@@ -1472,16 +1310,14 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
                 trace_mark(a.trace, wv, z - zs, 3);
                 lds_barrier();
                 trace_mark(a.trace, wv, z - zs, 4);
-                if constexpr (SD) {
-                    sd_in += pbytes;
-                    sd_div += pbytes;
-                    sd_out += pbytes;
-                    sd_rhs += pbytes;
-                    const int t_ = sd_oz;
-                    sd_oz = sd_on;
-                    sd_on = sd_od;
-                    sd_od = t_;
-                }
+                sd_in += pbytes;
+                sd_div += pbytes;
+                sd_out += pbytes;
+                sd_rhs += pbytes;
+                const int t_ = sd_oz;
+                sd_oz = sd_on;
+                sd_on = sd_od;
+                sd_od = t_;
                 if constexpr (!ROT) {
 #pragma unroll
                     for (int j = 0; j < RPW; ++j) {
@@ -1642,10 +1478,7 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
         // K <= 3 one plane (two: neutral for the Jacobi, -2 % for the GS,
         // which then spills a VGPR)
         constexpr int HPD = DMA && K == 4 ? 2 : PD;
-        if constexpr (T1D)
-            tbr_halo_wave<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S, true>(a, smem, z0, z1, y0, xs, zl, slots,
-                                                                                t1b);
-        else if constexpr (K == 4)
+        if constexpr (K == 4)
             tbr_halo_wave<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S>(a, smem, z0, z1, y0, xs, zl, slots);
         else
             tbr_halo_wave_call<K, NWR, RPW, PRE, HPD, MODE, F, SPLIT, PT, T0S>(a, smem, z0, z1, y0, xs, zl, slots);
@@ -1671,11 +1504,19 @@ __global__ __launch_bounds__((NWR + 1) * 64) void jacobi3d_tbr(TbrArgs a) {
 
 // Output rows per tile of the tall-tile shape for K levels.
 namespace {
+// One entry per tile shape: kShapes is the only list of them.  The cost model
+// picks from it, and tbr_launch_shape instantiates for each entry the kernels
+// its flags name (see there).
 struct TbrShape {
     int K, nwr, rpw;
     bool autopick;  // candidate for rows == 0
     bool masked = false;  // has a red-black GS instantiation with the 2-D mask (kMask2d)
-    int rows() const { return nwr * rpw + 2 - 2 * K; }
+    // has the Jacobi first-pass instantiations (kFirstRhs, kFirstRhs | kFirstZero) and, at K = 3 and 4,
+    // the shifting-queue ones (SHIFTQ); all on the LDS-DMA path
+    bool first = false;
+    int only = -1;  // kJacobi / kRbgs: instantiated for that solver only
+    constexpr int rows() const { return nwr * rpw + 2 - 2 * K; }
+    constexpr bool serves(int mode) const { return only < 0 || only == mode; }
 };
 // K = 4: (4, 11, 2) -- 16 output rows, one round of 256 workgroups at 1024^2 --
 // with the phi rows by LDS-DMA and the rhs by register prefetch, 161 VGPRs:
@@ -1692,9 +1533,21 @@ struct TbrShape {
 // its rollbacks).  (3, 10, 2) with the mask spills 17 VGPRs -- the unmasked
 // one sits at the cap of 168 -- so a masked solve at 3 levels takes the
 // in-place colour passes.
-constexpr TbrShape kShapes[] = {{3, 11, 2, true}, {3, 10, 2, true}, {3, 7, 3, false},
-                                {4, 7, 3, false}, {4, 11, 2, true, true}, {4, 10, 2, false}, {2, 11, 2, true},
-                                {2, 10, 2, true}, {2, 10, 3, false}, {2, 9, 2, true, true}, {1, 9, 2, true, true}};
+// (3, 7, 3) has Jacobi kernels only, (1, 9, 2) GS ones only (a single Jacobi
+// sweep is jacobi3d_sweep's).
+//                              K, waves, rows, auto, masked, first, only
+constexpr TbrShape kShapes[] = {{3, 11, 2, true, false, true},
+                                {3, 10, 2, true, false, true},
+                                {3, 7, 3, false, false, false, kJacobi},
+                                {4, 7, 3, false},
+                                {4, 11, 2, true, true, true},
+                                {4, 10, 2, false},
+                                {2, 11, 2, true, false, true},
+                                {2, 10, 2, true, false, true},
+                                {2, 10, 3, false},
+                                {2, 9, 2, true, true, true},
+                                {1, 9, 2, true, true, false, kRbgs}};
+constexpr int kNumShapes = sizeof(kShapes) / sizeof(kShapes[0]);
 
 int num_cus() {
     static int n = 0;
@@ -1721,6 +1574,69 @@ bool rbgs3d_tbr_mask_ok(int levels, int rows) {
         if (sh.K == levels && sh.masked && (rows == 0 || sh.rows() == rows)) return true;
     return false;
 }
+
+namespace {
+// The run-time choices of a launch, beside its shape.
+struct TbrPick {
+    int pd;       // prefetch depth (1: the LDS-DMA path where it fits)
+    bool pre;     // Jacobi: `div` holds the precomputed rhs
+    int first;    // Jacobi: 0, or the kFirst* flags
+    bool shiftq;  // Jacobi at K = 3 and 4: shifting queues (see tbr_launch)
+    bool masked;  // GS: TbrArgs::mask2d is set
+};
+template <int K, int NW, int RP, bool PRE, int PD, int MODE, int F = 0, bool SHIFTQ = false>
+void tbr_run(const TbrArgs &a, int blocks, hipStream_t s) {
+    hipLaunchKernelGGL((jacobi3d_tbr<K, NW, RP, PRE, PD, MODE, F, SHIFTQ>), dim3(blocks), dim3((NW + 1) * 64), 0, s, a);
+}
+// The kernels of one tile shape, and the launch of the one `p` asks for.  What
+// exists follows from the shape's kShapes flags:
+//   GS:     raw div at both prefetch depths; MASKED: the kMask2d kernel (LDS-DMA path);
+//   Jacobi: {PRE, raw div} x both prefetch depths; FIRST: the two first-pass
+//           forms and, at K = 3 and 4, the shifting-queue twins of those two
+//           and of the two plain LDS-DMA kernels.
+template <int MODE, int K, int NW, int RP, bool FIRST, bool MASKED>
+void tbr_launch_shape(const TbrArgs &a, int blocks, hipStream_t s, const TbrPick &p) {
+    if constexpr (MODE == kRbgs) {
+        if constexpr (MASKED) {
+            if (p.masked) return tbr_run<K, NW, RP, false, 1, MODE, kMask2d>(a, blocks, s);
+        }
+        if (p.pd == 2) return tbr_run<K, NW, RP, false, 2, MODE>(a, blocks, s);
+        return tbr_run<K, NW, RP, false, 1, MODE>(a, blocks, s);
+    } else {
+        if constexpr (FIRST) {  // (p.first and p.shiftq come with prefetch depth 1 only)
+            constexpr int kBoth = kFirstRhs | kFirstZero;
+            if constexpr (K == 3 || K == 4) {
+                if (p.shiftq) {
+                    if (p.first == kBoth) return tbr_run<K, NW, RP, false, 1, MODE, kBoth, true>(a, blocks, s);
+                    if (p.first == kFirstRhs) return tbr_run<K, NW, RP, false, 1, MODE, kFirstRhs, true>(a, blocks, s);
+                    if (p.pre) return tbr_run<K, NW, RP, true, 1, MODE, 0, true>(a, blocks, s);
+                    return tbr_run<K, NW, RP, false, 1, MODE, 0, true>(a, blocks, s);
+                }
+            }
+            if (p.first == kBoth) return tbr_run<K, NW, RP, false, 1, MODE, kBoth>(a, blocks, s);
+            if (p.first == kFirstRhs) return tbr_run<K, NW, RP, false, 1, MODE, kFirstRhs>(a, blocks, s);
+        }
+        if (p.pd == 2) {
+            if (p.pre) return tbr_run<K, NW, RP, true, 2, MODE>(a, blocks, s);
+            return tbr_run<K, NW, RP, false, 2, MODE>(a, blocks, s);
+        }
+        if (p.pre) return tbr_run<K, NW, RP, true, 1, MODE>(a, blocks, s);
+        return tbr_run<K, NW, RP, false, 1, MODE>(a, blocks, s);
+    }
+}
+// kShapes[I], for the solvers it serves
+template <int MODE, int I>
+void tbr_launch_entry(const TbrArgs &a, int blocks, hipStream_t s, const TbrPick &p) {
+    constexpr TbrShape S = kShapes[I];
+    if constexpr (S.serves(MODE)) tbr_launch_shape<MODE, S.K, S.nwr, S.rpw, S.first, S.masked>(a, blocks, s, p);
+}
+// the entry `sh` points to (tbr_launch picks only entries that serve MODE)
+template <int MODE, int... I>
+void tbr_dispatch(std::integer_sequence<int, I...>, const TbrShape *sh, const TbrArgs &a, int blocks, hipStream_t s,
+                  const TbrPick &p) {
+    ((sh == &kShapes[I] ? tbr_launch_entry<MODE, I>(a, blocks, s, p) : void()), ...);
+}
+}  // namespace
 
 // rows = output rows per tile (0: pick the shape and z-chunk by a cost model).
 // One workgroup fills a CU (LDS / VGPRs), so workgroups run in rounds of
@@ -1750,7 +1666,8 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
     int best_zlen = 0;
     double best_cost = 0.0;
     for (const TbrShape &sh : kShapes) {
-        if (sh.K != K || (rows ? sh.rows() != rows : !sh.autopick) || (masked && !sh.masked)) continue;
+        if (sh.K != K || !sh.serves(MODE) || (rows ? sh.rows() != rows : !sh.autopick) || (masked && !sh.masked))
+            continue;
         const int W = sh.rows(), NR = W + 2 * K;
         const long tiles = (long)nseg * ceil_div(a.ny - 2, W);
         for (int nzc = 1; nzc <= 64; ++nzc) {
@@ -1811,95 +1728,16 @@ static int tbr_launch(TbrArgs a, int K, int rows, int zchunk, bool pre, hipStrea
     const bool shiftq = MODE == kJacobi && pd == 1 &&
                         ((best->K == 3 && (shiftq_all || (nsteps % 6 != 0 && nsteps < 216))) ||
                          (best->K == 4 && (shiftq_all || nsteps < 48 * extra3)));
-#define CFD_TBR_L(KV, NW, RP, PR, PDV) \
-    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, PR, PDV, MODE>), dim3(blocks), dim3((NW + 1) * 64), 0, s, a)
-#define CFD_TBR(KV, NW, RP)                                                                   \
-    do {                                                                                      \
-        if constexpr (MODE == kRbgs) {                                                        \
-            if (pd == 2) CFD_TBR_L(KV, NW, RP, false, 2); else CFD_TBR_L(KV, NW, RP, false, 1); \
-        } else if (pd == 2) {                                                                 \
-            if (pre) CFD_TBR_L(KV, NW, RP, true, 2); else CFD_TBR_L(KV, NW, RP, false, 2);      \
-        } else {                                                                              \
-            if (pre) CFD_TBR_L(KV, NW, RP, true, 1); else CFD_TBR_L(KV, NW, RP, false, 1);      \
-        }                                                                                     \
-    } while (0)
-    // shapes with a first-pass variant (all on the LDS-DMA path); K = 3 ones
-    // also with shifting queues
-#define CFD_TBRF(KV, NW, RP)                                                                 \
-    do {                                                                                     \
-        if constexpr (MODE == kJacobi && (KV == 3 || KV == 4)) {                             \
-            if (shiftq) {                                                                    \
-                if (first == (kFirstRhs | kFirstZero))                                       \
-                    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kFirstRhs | kFirstZero, true>), \
-                                       dim3(blocks), dim3((NW + 1) * 64), 0, s, a);          \
-                else if (first == kFirstRhs)                                                 \
-                    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kFirstRhs, true>), \
-                                       dim3(blocks), dim3((NW + 1) * 64), 0, s, a);          \
-                else if (pre)                                                                \
-                    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, true, 1, MODE, 0, true>),   \
-                                       dim3(blocks), dim3((NW + 1) * 64), 0, s, a);          \
-                else                                                                         \
-                    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, 0, true>),  \
-                                       dim3(blocks), dim3((NW + 1) * 64), 0, s, a);          \
-                break;                                                                       \
-            }                                                                                \
-        }                                                                                    \
-        if constexpr (MODE == kJacobi) {                                                     \
-            if (first == (kFirstRhs | kFirstZero)) {                                         \
-                hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kFirstRhs | kFirstZero>), \
-                                   dim3(blocks), dim3((NW + 1) * 64), 0, s, a);              \
-                break;                                                                       \
-            }                                                                                \
-            if (first == kFirstRhs) {                                                        \
-                hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kFirstRhs>),     \
-                                   dim3(blocks), dim3((NW + 1) * 64), 0, s, a);              \
-                break;                                                                       \
-            }                                                                                \
-        }                                                                                    \
-        CFD_TBR(KV, NW, RP);                                                                 \
-    } while (0)
-    const int code = best->K * 100 + best->nwr * 10 + best->rpw;
-    if constexpr (MODE == kRbgs) {
-        if (masked) {  // the kShapes entries with `masked`, LDS-DMA path
-#define CFD_TBR_M(KV, NW, RP)                                                                             \
-    hipLaunchKernelGGL((jacobi3d_tbr<KV, NW, RP, false, 1, MODE, kMask2d>), dim3(blocks), dim3((NW + 1) * 64), 0, \
-                       s, a)
-            switch (code) {
-                case 4 * 100 + 11 * 10 + 2: CFD_TBR_M(4, 11, 2); break;
-                case 2 * 100 + 9 * 10 + 2: CFD_TBR_M(2, 9, 2); break;
-                default: CFD_TBR_M(1, 9, 2); break;
-            }
-#undef CFD_TBR_M
-            CFD_LAUNCH_CHECK();
-            return CFD_OK;
-        }
-    }
-    // only the CFD_TBRF shapes below have first-pass instantiations; a first
-    // pass on any other shape would silently run as a plain pass (rhs_out
-    // never written, phi read from `out`)
-    if (first && code != 3 * 100 + 11 * 10 + 2 && code != 3 * 100 + 10 * 10 + 2 &&
-        code != 4 * 100 + 11 * 10 + 2 && code != 2 * 100 + 11 * 10 + 2 && code != 2 * 100 + 10 * 10 + 2 &&
-        code != 2 * 100 + 9 * 10 + 2) {
+    // only shapes with `first` have first-pass instantiations; a first pass
+    // on any other shape would silently run as a plain pass (rhs_out never
+    // written, phi read from `out`)
+    if (first && !best->first) {
         set_error("jacobi3d_tbr: tile shape (%d levels, %d x %d rows) has no first-pass variant", best->K,
                   best->nwr, best->rpw);
         return CFD_E_INVALID;
     }
-    switch (code) {
-        case 3 * 100 + 11 * 10 + 2: CFD_TBRF(3, 11, 2); break;
-        case 3 * 100 + 10 * 10 + 2: CFD_TBRF(3, 10, 2); break;
-        case 1 * 100 + 9 * 10 + 2: if constexpr (MODE == kRbgs) CFD_TBR(1, 9, 2); break;
-        case 3 * 100 + 7 * 10 + 3: if constexpr (MODE == kJacobi) CFD_TBR(3, 7, 3); break;
-        case 4 * 100 + 7 * 10 + 3: CFD_TBR(4, 7, 3); break;
-        case 4 * 100 + 11 * 10 + 2: CFD_TBRF(4, 11, 2); break;
-        case 4 * 100 + 10 * 10 + 2: CFD_TBR(4, 10, 2); break;
-        case 2 * 100 + 11 * 10 + 2: CFD_TBRF(2, 11, 2); break;
-        case 2 * 100 + 10 * 10 + 2: CFD_TBRF(2, 10, 2); break;
-        case 2 * 100 + 9 * 10 + 2: CFD_TBRF(2, 9, 2); break;
-        default: CFD_TBR(2, 10, 3); break;
-    }
-#undef CFD_TBRF
-#undef CFD_TBR
-#undef CFD_TBR_L
+    tbr_dispatch<MODE>(std::make_integer_sequence<int, kNumShapes>{}, best, a, blocks, s,
+                       TbrPick{pd, pre, first, shiftq, masked});
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

@@ -943,7 +943,8 @@ int cfd_release_thread_resources(void);
  * halo received, levels done, published into the same buffer. */
 int cfd_set_small2d_gs_trace(void *buf, size_t bytes);
 /* Diagnostics, in a library built with -DCFD_TBR_TRACE (scripts/build_variant.sh;
- * a no-op otherwise): the 3-D tall-tile kernels' workgroup 0 records, per wave,
+ * the only compile-time switch jacobi3d_tbr.hip has left; a no-op otherwise):
+ * the 3-D tall-tile kernels' workgroup 0 records, per wave,
  * the shader clock at 5 points (step entry, before / after each of the step's
  * two barriers) of z-steps 200..263 into buf, layout [wave][64][5] u64 (40 KiB,
  * 16 waves; NULL: off, the default). */

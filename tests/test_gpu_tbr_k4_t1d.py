@@ -1,21 +1,28 @@
-"""The K = 4 Jacobi pass with two level-1 tile buffers (jacobi3d_tbr<4, 11, 2>
-with T1D): bit-identical to K single sweeps (oracle.jacobi3d).
+"""The K = 4 Jacobi pass on (4, 11, 2) tiles (jacobi3d_tbr<4, 11, 2>):
+bit-identical to K single sweeps (oracle.jacobi3d).
 
-Step z of a z-chunk reads level 1 from buffer (z - zs) & 1 and the row waves
-store the level 1 they compute into the other one during phase R; the halo
-wave stores its x-halo chunks of level 1 into the buffer being read, in phase
-W.  What can go wrong is the parity: between the halo wave and the row waves
-(seen only at the edge between two x-segments, so 264 columns), and at the
-end of a chunk, where the rotated march rounds its step count up to a multiple
-of 3.  Grid (100, 12, 264) with z-chunks of 90..95 planes gives step counts
+What the file guards:
+* the pass at the edge between two x-segments (264 columns), where the halo
+  wave's x-halo chunks and the row waves' cells meet;
+* the period-3 round-up of the step count: the rotated march runs whole
+  groups of 3 steps, so the end of a chunk sees 0, 1 or 2 extra steps;
+* the clipped last chunk, which runs the shifting-queue kernel.
+
+The cases were introduced with a variant that double-buffered the level-1
+tile (T1D: step z read level 1 from buffer (z - zs) & 1 and stored into the
+other one, so the parity between the halo wave and the row waves, and at the
+end of a chunk, could go wrong).  That variant measured slower and was
+removed; the cases stay for what they cover of the kernel that shipped.
+
+Grid (100, 12, 264) with z-chunks of 90..95 planes gives step counts
 96..101 (planes + 6), i.e. both parities of the last step x all three
 round-ups, a partial y-tile, and a clipped last chunk of 10..5 planes that
 runs the shifting-queue instantiation with 16..11 steps (both parities again).
 (40, 31, 520) adds three segments with a partial last one and two y-tiles,
 (11, 40, 16) a single segment; their z-chunks 0, 5, 7 are the whole grid and
 short chunks.  Every first-pass form runs: zero start with a workspace, a
-guess with a workspace, and no workspace; 4, 8 and 9 iterations make a T1D
-pass feed a pass in either ping-pong direction and a remainder pass.
+guess with a workspace, and no workspace; 4, 8 and 9 iterations make a pass
+feed a pass in either ping-pong direction and a remainder pass.
 """
 import ctypes
 import functools
