@@ -1,9 +1,9 @@
 // fields3d.hip -- the 3-D projection step around the 3-D pressure solves, for
 // gfx950: fused advection-diffusion predictor, divergence, gradient +
 // projection, lid-driven cavity walls, the cylinder channel's boundary
-// conditions with the immersed-boundary forcing, the vorticity, the energy /
-// clip epilogue and the flow statistics' running sums on (nz, ny, nx) float32
-// fields u, v, w (x fastest; E/W = x+-1, N/S = y+-1, U/D = z+-1).
+// conditions with the immersed-boundary forcing, the vorticity and the energy /
+// clip epilogue on (nz, ny, nx) float32 fields u, v, w (x fastest; E/W = x+-1,
+// N/S = y+-1, U/D = z+-1).
 //
 // The arithmetic is the project's own 3-D generalisation of the v5 templates
 // (fields2d.hip), every 2-D coefficient kept and a z term appended to each
@@ -445,286 +445,6 @@ static int energy3_slot(hipStream_t s) {
     return slots[{dev, s}] = used[dev]++;
 }
 
-// Flow statistics: the moments u, v, w, uu, vv, ww, uv, uw, vw (and nu_t when
-// NM == 10) of every cell, each formed in double from the float32 values
-// loaded (a product of two float32 values is exact in double), added with a
-// weight into float64 running sums.  No atomics and no workspace; the order of
-// every sum depends on the shape alone: the same bits run to run.
-template <int NM>
-__device__ inline void stats_terms(float a, float b, float d, [[maybe_unused]] float e, double (&t)[NM]) {
-    const double x = (double)a, y = (double)b, z = (double)d;
-    t[0] = x;
-    t[1] = y;
-    t[2] = z;
-    t[3] = x * x;
-    t[4] = y * y;
-    t[5] = z * z;
-    t[6] = x * y;
-    t[7] = x * z;
-    t[8] = y * z;
-    if constexpr (NM == 10) t[9] = (double)e;
-}
-
-// Span mode: acc[m, p] += weight * sum_k t_m(k, p) over the columns p of the
-// (ny, nx) plane taken as one flat index (any nx: no row structure is used).
-// A workgroup owns 64 adjacent columns; its kStatsWaves waves split z into
-// contiguous chunks of ceil(nz / kStatsWaves) planes (the last ones may be
-// short or empty).  Each wave marches its chunk in plane order, kStatsUnroll
-// planes' loads issued together, into NM double sums per lane; the waves'
-// partials meet in LDS and are added in wave order, multiplied by weight once
-// and added to acc once.  So a column's sum is ((c_0 + c_1) + ...) + c_7 with
-// c_q the in-order sum of chunk q.
-constexpr int kStatsWaves = 8;
-// two planes: at four the kernels hold 120 (nm = 9) and 158 (nm = 10) VGPRs and one or two
-// workgroups fit a CU; at two they are faster at 600 x 180 x 120
-constexpr int kStatsUnroll = 2;
-constexpr unsigned kStatsMaxBlocks = 1u << 20;  // the kernels stride beyond
-
-template <int NM>
-__global__ __launch_bounds__(kStatsWaves *kWave) void k_flow_stats3d_span(
-    const float *__restrict__ u, const float *__restrict__ v, const float *__restrict__ w,
-    const float *__restrict__ nut, double *__restrict__ acc, int nz, size_t plane, size_t tiles, double weight) {
-    constexpr int U = kStatsUnroll;
-    __shared__ double part[kStatsWaves][NM][kWave];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    const int chunk = (nz + kStatsWaves - 1) / kStatsWaves;
-    const int k0 = wv * chunk < nz ? wv * chunk : nz, k1 = k0 + chunk < nz ? k0 + chunk : nz;
-    for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const size_t p = tile * kWave + lane;
-        double s[NM];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) s[m] = 0.0;
-        if (p < plane) {
-            size_t c = (size_t)k0 * plane + p;
-            int k = k0;
-            for (; k + U <= k1; k += U, c += U * plane) {
-                float a[U], b[U], d[U], e[U];
-#pragma unroll
-                for (int q = 0; q < U; ++q) {
-                    a[q] = u[c + q * plane];
-                    b[q] = v[c + q * plane];
-                    d[q] = w[c + q * plane];
-                    e[q] = NM == 10 ? nut[c + q * plane] : 0.0f;
-                }
-#pragma unroll
-                for (int q = 0; q < U; ++q) {
-                    double t[NM];
-                    stats_terms<NM>(a[q], b[q], d[q], e[q], t);
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) s[m] += t[m];
-                }
-            }
-            for (; k < k1; ++k, c += plane) {
-                double t[NM];
-                stats_terms<NM>(u[c], v[c], w[c], NM == 10 ? nut[c] : 0.0f, t);
-#pragma unroll
-                for (int m = 0; m < NM; ++m) s[m] += t[m];
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < NM; ++m) part[wv][m][lane] = s[m];
-        __syncthreads();
-        for (int q = threadIdx.x; q < NM * kWave; q += kStatsWaves * kWave) {
-            const int m = q / kWave, l = q % kWave;
-            const size_t pp = tile * kWave + l;
-            if (pp < plane) {
-                double r = part[0][m][l];
-#pragma unroll
-                for (int x = 1; x < kStatsWaves; ++x) r += part[x][m][l];
-                const size_t o = (size_t)m * plane + pp;
-                acc[o] = acc[o] + weight * r;
-            }
-        }
-        __syncthreads();  // part is rewritten by the next tile
-    }
-}
-
-// Full mode: acc[m, c] += weight * t_m(c), a read-modify-write of NM doubles
-// per cell.  VEC (n even, fields 8-byte and acc 16-byte aligned): a thread
-// takes two adjacent cells, the fields as float2 and each moment's
-// accumulators as one 16-byte load and store; else one cell per thread.
-template <int NM, bool VEC>
-__global__ __launch_bounds__(256) void k_flow_stats3d_full(const float *__restrict__ u, const float *__restrict__ v,
-                                                           const float *__restrict__ w,
-                                                           const float *__restrict__ nut, double *__restrict__ acc,
-                                                           size_t n, double weight) {
-    constexpr int C = VEC ? 2 : 1;
-    const size_t items = n / C;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
-        const size_t c = i * C;
-        double t[C][NM];
-        if constexpr (VEC) {
-            const float2 a = *reinterpret_cast<const float2 *>(u + c), b = *reinterpret_cast<const float2 *>(v + c);
-            const float2 d = *reinterpret_cast<const float2 *>(w + c);
-            float2 e = {0.0f, 0.0f};
-            if constexpr (NM == 10) e = *reinterpret_cast<const float2 *>(nut + c);
-            stats_terms<NM>(a.x, b.x, d.x, e.x, t[0]);
-            stats_terms<NM>(a.y, b.y, d.y, e.y, t[1]);
-            double2 o[NM];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) o[m] = *reinterpret_cast<const double2 *>(acc + (size_t)m * n + c);
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                o[m].x = o[m].x + weight * t[0][m];
-                o[m].y = o[m].y + weight * t[1][m];
-                *reinterpret_cast<double2 *>(acc + (size_t)m * n + c) = o[m];
-            }
-        } else {
-            stats_terms<NM>(u[c], v[c], w[c], NM == 10 ? nut[c] : 0.0f, t[0]);
-            double o[NM];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) o[m] = acc[(size_t)m * n + c];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) acc[(size_t)m * n + c] = o[m] + weight * t[0][m];
-        }
-    }
-}
-
-// Flow statistics with the passive scalar: the NM - 5 moments above (9, or 10
-// with nu_t: stats_terms<NM - 5>, untouched), then T, TT, uT, vT, wT: NM = 14
-// or 15.  The kernels are siblings of the two above with one more 4-byte load
-// per cell; every sum has the order it has there, so the first NM - 5 planes
-// of acc get the bits cfd_flow_stats3d_f32 gives them.
-template <int NM>
-__device__ inline void scalar_stats_terms(float a, float b, float d, float e, float f, double (&t)[NM]) {
-    constexpr int B = NM - 5;
-    static_assert(B == 9 || B == 10, "14 or 15 moments");
-    double base[B];
-    stats_terms<B>(a, b, d, e, base);
-#pragma unroll
-    for (int m = 0; m < B; ++m) t[m] = base[m];
-    const double s = (double)f;
-    t[B] = s;
-    t[B + 1] = s * s;
-    t[B + 2] = base[0] * s;
-    t[B + 3] = base[1] * s;
-    t[B + 4] = base[2] * s;
-}
-
-// two planes, as kStatsUnroll, by measurement: at four the span kernels hold
-// 160 (nm = 14) and 236 (nm = 15) VGPRs and took 47.9 and 56.6 us at
-// 600 x 180 x 120 against 36.5 and 42.7 us at two
-constexpr int kScalarStatsUnroll = 2;
-
-// Span mode, k_flow_stats3d_span's chunks and wave order.  The partials of
-// all NM moments would take 8 * NM * 64 doubles of LDS (57,344 B at NM = 14),
-// two workgroups per CU; the waves' partials go through LDS in two halves of
-// the moments instead (8 * ceil(NM / 2) * 64 doubles, 28,672 or 32,768 B), each
-// added in wave order as there: the LDS traffic is reordered, no sum is.
-// Measured against the one-pass combine: 36.5 against 38.5 us (nm = 14), 42.7
-// against 46.1 us (nm = 15).
-template <int NM>
-__global__ __launch_bounds__(kStatsWaves *kWave) void k_flow_scalar_stats3d_span(
-    const float *__restrict__ u, const float *__restrict__ v, const float *__restrict__ w,
-    const float *__restrict__ nut, const float *__restrict__ T, double *__restrict__ acc, int nz, size_t plane,
-    size_t tiles, double weight) {
-    constexpr int U = kScalarStatsUnroll;
-    constexpr bool NUT = NM == 15;
-    constexpr int H = (NM + 1) / 2;  // moments per half
-    __shared__ double part[kStatsWaves][H][kWave];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    const int chunk = (nz + kStatsWaves - 1) / kStatsWaves;
-    const int k0 = wv * chunk < nz ? wv * chunk : nz, k1 = k0 + chunk < nz ? k0 + chunk : nz;
-    for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const size_t p = tile * kWave + lane;
-        double s[NM];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) s[m] = 0.0;
-        if (p < plane) {
-            size_t c = (size_t)k0 * plane + p;
-            int k = k0;
-            for (; k + U <= k1; k += U, c += U * plane) {
-                float a[U], b[U], d[U], e[U], f[U];
-#pragma unroll
-                for (int q = 0; q < U; ++q) {
-                    a[q] = u[c + q * plane];
-                    b[q] = v[c + q * plane];
-                    d[q] = w[c + q * plane];
-                    e[q] = NUT ? nut[c + q * plane] : 0.0f;
-                    f[q] = T[c + q * plane];
-                }
-#pragma unroll
-                for (int q = 0; q < U; ++q) {
-                    double t[NM];
-                    scalar_stats_terms<NM>(a[q], b[q], d[q], e[q], f[q], t);
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) s[m] += t[m];
-                }
-            }
-            for (; k < k1; ++k, c += plane) {
-                double t[NM];
-                scalar_stats_terms<NM>(u[c], v[c], w[c], NUT ? nut[c] : 0.0f, T[c], t);
-#pragma unroll
-                for (int m = 0; m < NM; ++m) s[m] += t[m];
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int m0 = h * H, mh = h == 0 ? H : NM - H;  // this half: moments m0 .. m0 + mh - 1
-#pragma unroll
-            for (int m = 0; m < mh; ++m) part[wv][m][lane] = s[m0 + m];
-            __syncthreads();
-            for (int q = threadIdx.x; q < mh * kWave; q += kStatsWaves * kWave) {
-                const int m = q / kWave, l = q % kWave;
-                const size_t pp = tile * kWave + l;
-                if (pp < plane) {
-                    double r = part[0][m][l];
-#pragma unroll
-                    for (int x = 1; x < kStatsWaves; ++x) r += part[x][m][l];
-                    const size_t o = (size_t)(m0 + m) * plane + pp;
-                    acc[o] = acc[o] + weight * r;
-                }
-            }
-            __syncthreads();  // part is rewritten by the next half or tile
-        }
-    }
-}
-
-// Full mode, k_flow_stats3d_full with T: VEC needs T 8-byte aligned too.
-template <int NM, bool VEC>
-__global__ __launch_bounds__(256) void k_flow_scalar_stats3d_full(
-    const float *__restrict__ u, const float *__restrict__ v, const float *__restrict__ w,
-    const float *__restrict__ nut, const float *__restrict__ T, double *__restrict__ acc, size_t n, double weight) {
-    constexpr int C = VEC ? 2 : 1;
-    constexpr bool NUT = NM == 15;
-    const size_t items = n / C;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
-        const size_t c = i * C;
-        double t[C][NM];
-        if constexpr (VEC) {
-            const float2 a = *reinterpret_cast<const float2 *>(u + c), b = *reinterpret_cast<const float2 *>(v + c);
-            const float2 d = *reinterpret_cast<const float2 *>(w + c), f = *reinterpret_cast<const float2 *>(T + c);
-            float2 e = {0.0f, 0.0f};
-            if constexpr (NUT) e = *reinterpret_cast<const float2 *>(nut + c);
-            scalar_stats_terms<NM>(a.x, b.x, d.x, e.x, f.x, t[0]);
-            scalar_stats_terms<NM>(a.y, b.y, d.y, e.y, f.y, t[1]);
-            // the accumulators in two halves of the moments: 70 VGPRs against 128 (nm = 14) and
-            // 134 (nm = 15) with all of them loaded first; the times did not tell the two apart
-            constexpr int H = (NM + 1) / 2;
-#pragma unroll
-            for (int m0 = 0; m0 < NM; m0 += H) {
-                double2 o[H];
-#pragma unroll
-                for (int m = m0; m < m0 + H && m < NM; ++m)
-                    o[m - m0] = *reinterpret_cast<const double2 *>(acc + (size_t)m * n + c);
-#pragma unroll
-                for (int m = m0; m < m0 + H && m < NM; ++m) {
-                    o[m - m0].x = o[m - m0].x + weight * t[0][m];
-                    o[m - m0].y = o[m - m0].y + weight * t[1][m];
-                    *reinterpret_cast<double2 *>(acc + (size_t)m * n + c) = o[m - m0];
-                }
-            }
-        } else {
-            scalar_stats_terms<NM>(u[c], v[c], w[c], NUT ? nut[c] : 0.0f, T[c], t[0]);
-            double o[NM];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) o[m] = acc[(size_t)m * n + c];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) acc[(size_t)m * n + c] = o[m] + weight * t[0][m];
-        }
-    }
-}
-
 static dim3 grid3d(int nz, int ny, int nx) { return dim3(ceil_div(nx, 256), ny, nz); }
 
 static thread_local int g_last_pred3[2] = {-1, 0};
@@ -984,83 +704,6 @@ int cfd_energy_mean_clip3d_f32(float *u, float *v, float *w, size_t n, double *o
     size_t nb = (n + 4095) / 4096;  // ~16 cells per thread
     if (nb > (size_t)kEnergy3Blocks) nb = kEnergy3Blocks;
     hipLaunchKernelGGL(k_energy_mean_clip3d, dim3((unsigned)nb), dim3(256), 0, s, u, v, w, n, out, lo, hi, slot);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
-}
-
-int cfd_flow_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t, double *acc, int nz,
-                         int ny, int nx, double weight, int span_average, void *stream) {
-    CFD_REQUIRE(u && v && w && acc, "flow_stats3d_f32: null pointer");
-    CFD_REQUIRE(u != v && u != w && v != w, "flow_stats3d_f32: u, v, w must be three arrays");
-    CFD_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, "flow_stats3d_f32: bad shape (%d, %d, %d): every dimension >= 1", nz, ny,
-                nx);
-    CFD_REQUIRE(weight - weight == 0.0, "flow_stats3d_f32: weight %g is not finite", weight);
-    CFD_REQUIRE(span_average == 0 || span_average == 1, "flow_stats3d_f32: span_average %d is not 0 or 1",
-                span_average);
-    hipStream_t s = as_stream(stream);
-    const size_t plane = (size_t)ny * nx, n = plane * (size_t)nz;
-    if (span_average) {
-        const size_t tiles = (plane + kWave - 1) / kWave;
-        const dim3 g((unsigned)(tiles < kStatsMaxBlocks ? tiles : kStatsMaxBlocks)), b(kStatsWaves * kWave);
-        if (nu_t)
-            hipLaunchKernelGGL(k_flow_stats3d_span<10>, g, b, 0, s, u, v, w, nu_t, acc, nz, plane, tiles, weight);
-        else
-            hipLaunchKernelGGL(k_flow_stats3d_span<9>, g, b, 0, s, u, v, w, nu_t, acc, nz, plane, tiles, weight);
-    } else {
-        auto al = [](const void *p_, uintptr_t m) { return ((uintptr_t)p_ & m) == 0; };
-        const bool vec = n % 2 == 0 && al(u, 7) && al(v, 7) && al(w, 7) && al(nu_t, 7) && al(acc, 15);
-        const size_t blocks = ((vec ? n / 2 : n) + 255) / 256;
-        const dim3 g((unsigned)(blocks < kStatsMaxBlocks ? blocks : kStatsMaxBlocks)), b(256);
-#define CFD_STATS_FULL(NM, VEC) hipLaunchKernelGGL((k_flow_stats3d_full<NM, VEC>), g, b, 0, s, u, v, w, nu_t, acc, n, weight)
-        if (nu_t) {
-            if (vec) CFD_STATS_FULL(10, true);
-            else CFD_STATS_FULL(10, false);
-        } else {
-            if (vec) CFD_STATS_FULL(9, true);
-            else CFD_STATS_FULL(9, false);
-        }
-#undef CFD_STATS_FULL
-    }
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
-}
-
-int cfd_flow_scalar_stats3d_f32(const float *u, const float *v, const float *w, const float *nu_t, const float *T,
-                                double *acc, int nz, int ny, int nx, double weight, int span_average, void *stream) {
-    CFD_REQUIRE(u && v && w && T && acc, "flow_scalar_stats3d_f32: null pointer");
-    CFD_REQUIRE(u != v && u != w && v != w, "flow_scalar_stats3d_f32: u, v, w must be three arrays");  // T may be one
-    CFD_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1, "flow_scalar_stats3d_f32: bad shape (%d, %d, %d): every dimension >= 1",
-                nz, ny, nx);
-    CFD_REQUIRE(weight - weight == 0.0, "flow_scalar_stats3d_f32: weight %g is not finite", weight);
-    CFD_REQUIRE(span_average == 0 || span_average == 1, "flow_scalar_stats3d_f32: span_average %d is not 0 or 1",
-                span_average);
-    hipStream_t s = as_stream(stream);
-    const size_t plane = (size_t)ny * nx, n = plane * (size_t)nz;
-    if (span_average) {
-        const size_t tiles = (plane + kWave - 1) / kWave;
-        const dim3 g((unsigned)(tiles < kStatsMaxBlocks ? tiles : kStatsMaxBlocks)), b(kStatsWaves * kWave);
-        if (nu_t)
-            hipLaunchKernelGGL(k_flow_scalar_stats3d_span<15>, g, b, 0, s, u, v, w, nu_t, T, acc, nz, plane, tiles,
-                               weight);
-        else
-            hipLaunchKernelGGL(k_flow_scalar_stats3d_span<14>, g, b, 0, s, u, v, w, nu_t, T, acc, nz, plane, tiles,
-                               weight);
-    } else {
-        auto al = [](const void *p_, uintptr_t m) { return ((uintptr_t)p_ & m) == 0; };
-        const bool vec = n % 2 == 0 && al(u, 7) && al(v, 7) && al(w, 7) && al(nu_t, 7) && al(T, 7) && al(acc, 15);
-        const size_t blocks = ((vec ? n / 2 : n) + 255) / 256;
-        const dim3 g((unsigned)(blocks < kStatsMaxBlocks ? blocks : kStatsMaxBlocks)), b(256);
-#define CFD_STATS_FULL(NM, VEC) \
-    hipLaunchKernelGGL((k_flow_scalar_stats3d_full<NM, VEC>), g, b, 0, s, u, v, w, nu_t, T, acc, n, weight)
-        if (nu_t) {
-            if (vec) CFD_STATS_FULL(15, true);
-            else CFD_STATS_FULL(15, false);
-        } else {
-            if (vec) CFD_STATS_FULL(14, true);
-            else CFD_STATS_FULL(14, false);
-        }
-#undef CFD_STATS_FULL
-    }
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }

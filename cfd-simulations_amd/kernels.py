@@ -656,6 +656,20 @@ def compute_vorticity3d(u, v, w, dx, dy, dz, mask=None, components=False, absmax
     return (comp[0], comp[1], comp[2], mag) if components else mag
 
 
+def _accumulate_stats3d(symbol, fields, nm, shape, acc, weight, span_average):
+    """Check ``acc`` ((nm, ny, nx) with ``span_average``, else (nm, nz, ny, nx),
+    float64, on the fields' device) and call ``symbol`` on ``fields``."""
+    nz, ny, nx = shape
+    want = (nm, ny, nx) if span_average else (nm, nz, ny, nx)
+    dev = fields[0].device
+    if acc.dtype != torch.float64 or tuple(acc.shape) != want or acc.device != dev:
+        raise ValueError(f"acc must be a float64 {want} array on {dev}, got {tuple(acc.shape)} {acc.dtype} "
+                         f"on {acc.device}")
+    call(symbol, *(ptr(f) for f in fields), ptr(acc), nz, ny, nx, float(weight), 1 if span_average else 0,
+         stream_handle())
+    return acc
+
+
 def accumulate_flow_stats3d(u, v, w, acc, weight, span_average, nu_t=None):
     """acc += weight * moments of (nz, ny, nx) float32 u, v, w
     (cfd_flow_stats3d_f32).  The moments are u, v, w, uu, vv, ww, uv, uw, vw
@@ -663,15 +677,9 @@ def accumulate_flow_stats3d(u, v, w, acc, weight, span_average, nu_t=None):
     float64: (nm, nz, ny, nx), or with ``span_average`` (nm, ny, nx), which
     receives weight times the float64 sum over z.  Deterministic (no atomics);
     every cell counts.  Returns acc."""
-    nz, ny, nx = _fields3d(u, v=v, w=w, nu_t=nu_t)
-    nm = 9 if nu_t is None else 10
-    want = (nm, ny, nx) if span_average else (nm, nz, ny, nx)
-    if acc.dtype != torch.float64 or tuple(acc.shape) != want or acc.device != u.device:
-        raise ValueError(f"acc must be a float64 {want} array on {u.device}, got {tuple(acc.shape)} {acc.dtype} "
-                         f"on {acc.device}")
-    call("cfd_flow_stats3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), ptr(acc), nz, ny, nx, float(weight),
-         1 if span_average else 0, stream_handle())
-    return acc
+    shape = _fields3d(u, v=v, w=w, nu_t=nu_t)
+    return _accumulate_stats3d("cfd_flow_stats3d_f32", (u, v, w, nu_t), 9 if nu_t is None else 10, shape, acc, weight,
+                               span_average)
 
 
 def accumulate_flow_scalar_stats3d(u, v, w, T, acc, weight, span_average, nu_t=None):
@@ -680,15 +688,9 @@ def accumulate_flow_scalar_stats3d(u, v, w, T, acc, weight, span_average, nu_t=N
     so ``acc`` has 14 planes, or 15 with ``nu_t``.  The first 9 (10) planes
     get exactly the bits accumulate_flow_stats3d gives them.  ``T`` may be
     one of u, v, w.  Returns acc."""
-    nz, ny, nx = _fields3d(u, v=v, w=w, nu_t=nu_t, T=T)
-    nm = 14 if nu_t is None else 15
-    want = (nm, ny, nx) if span_average else (nm, nz, ny, nx)
-    if acc.dtype != torch.float64 or tuple(acc.shape) != want or acc.device != u.device:
-        raise ValueError(f"acc must be a float64 {want} array on {u.device}, got {tuple(acc.shape)} {acc.dtype} "
-                         f"on {acc.device}")
-    call("cfd_flow_scalar_stats3d_f32", ptr(u), ptr(v), ptr(w), ptr(nu_t), ptr(T), ptr(acc), nz, ny, nx,
-         float(weight), 1 if span_average else 0, stream_handle())
-    return acc
+    shape = _fields3d(u, v=v, w=w, nu_t=nu_t, T=T)
+    return _accumulate_stats3d("cfd_flow_scalar_stats3d_f32", (u, v, w, nu_t, T), 14 if nu_t is None else 15, shape,
+                               acc, weight, span_average)
 
 
 def persistent_failures(stream=None) -> int:
