@@ -101,6 +101,16 @@ PROTOTYPES = {
                                          c_double, c_float, c_int, P]),
     "cfd_predictor3d_les_zper_f32": (c_int, [P, P, P, c_float, c_float, c_double, P, P, P, P, P, c_int, c_int,
                                              c_int, c_double, c_double, c_double, c_float, c_int, P]),
+    "cfd_predictor3d_buoy_f32": (c_int, [P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P, P, c_int,
+                                         c_int, c_int, c_double, c_double, c_double, c_float, c_int, P]),
+    "cfd_predictor3d_les_buoy_f32": (c_int, [P, P, P, P, c_float, c_float, c_double, c_float, c_float, c_float,
+                                             c_float, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
+                                             c_double, c_float, c_int, P]),
+    "cfd_predictor3d_buoy_zper_f32": (c_int, [P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, P, P, P,
+                                              c_int, c_int, c_int, c_double, c_double, c_double, c_float, c_int, P]),
+    "cfd_predictor3d_les_buoy_zper_f32": (c_int, [P, P, P, P, c_float, c_float, c_double, c_float, c_float, c_float,
+                                                  c_float, P, P, P, P, P, c_int, c_int, c_int, c_double, c_double,
+                                                  c_double, c_float, c_int, P]),
     "cfd_set_predictor3d_config": (c_int, [c_int, c_int, c_int]),
     "cfd_get_last_predictor3d_path": (c_int, [ctypes.POINTER(c_int)]),
     "cfd_divergence3d_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_double, c_double, c_double, P, P]),

@@ -12,6 +12,7 @@
 // All indexing is 64-bit.
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #include "common.hpp"
 #include "internal.hpp"
@@ -55,8 +56,17 @@ struct Pred3Nu {
     float *nut;
     float c2, art;
 };
+// the trailing mode arguments of k_predictor3d, picked by type
+__device__ inline Pred3Nu pred3_mode_nu() { return {}; }
+__device__ inline Pred3Nu pred3_mode_nu(const Pred3Nu &m) { return m; }
+__device__ inline Pred3Nu pred3_mode_nu(const Pred3Buoy &) { return {}; }
+__device__ inline Pred3Nu pred3_mode_nu(const Pred3Nu &m, const Pred3Buoy &) { return m; }
+__device__ inline Pred3Buoy pred3_mode_buoy(const Pred3Buoy &b) { return b; }
+__device__ inline Pred3Buoy pred3_mode_buoy(const Pred3Nu &, const Pred3Buoy &b) { return b; }
 // M: one Pred3Nu for the array and LES modes, empty for the scalar one (whose
-// argument list, and with it its code, stays what it was before the modes)
+// argument list, and with it its code, stays what it was before the modes);
+// then one Pred3Buoy for the buoyant form (scalar and LES only), which adds
+// dt * (b_f * (T - t_ref)) to the interior cells' f* (pred_planes.hpp: BUOY)
 template <bool SUPG, int NM, bool ZP, typename... M>
 __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u, const float *__restrict__ v,
                                                      const float *__restrict__ w, float nu,
@@ -68,7 +78,9 @@ __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u
     const float uc = u[c], vc = v[c], wc = w[c];
     float uo = uc, vo = vc, wo = wc, t = 0.0f;  // the six faces keep f (tau, nu_t: 0)
     [[maybe_unused]] float nt = 0.0f;
-    [[maybe_unused]] const Pred3Nu m = {mode...};
+    constexpr bool BUOY = (std::is_same_v<M, Pred3Buoy> || ...);
+    static_assert(!BUOY || NM != kNu3Array, "buoyancy: scalar and LES viscosity only");
+    [[maybe_unused]] const Pred3Nu m = pred3_mode_nu(mode...);
     if (interior3z<ZP>(k, j, i, nz, ny, nx)) {
         CFD_3D_UD(ZP)
         const Nb7 fu = {uc, u[c + 1], u[c - 1], u[c + sy], u[c - sy], u[cu], u[cd]};
@@ -83,6 +95,13 @@ __global__ __launch_bounds__(256) void k_predictor3d(const float *__restrict__ u
         uo = pred3_cell<SUPG>(uc, vc, wc, fu, t, nu, dt, kk);
         vo = pred3_cell<SUPG>(uc, vc, wc, fv, t, nu, dt, kk);
         wo = pred3_cell<SUPG>(uc, vc, wc, fw, t, nu, dt, kk);
+        if constexpr (BUOY) {
+            const Pred3Buoy bm = pred3_mode_buoy(mode...);
+            const float th = bm.T[c] - bm.t_ref;
+            uo = uo + dt * (bm.bx * th);
+            vo = vo + dt * (bm.by * th);
+            wo = wo + dt * (bm.bz * th);
+        }
     }
     us[c] = uo;
     vs[c] = vo;
@@ -458,22 +477,23 @@ using namespace cfd;
     CFD_REQUIRE((nz) >= 3 && (ny) >= 3 && (nx) >= 3 && (ny) <= 65535 && (nz) <= 65535,                       \
                 "%s: bad 3-D shape (%d, %d, %d): every dimension 3 .. 65535 (nx: any >= 3)", who, nz, ny, nx)
 
-extern "C" {
-
-// The three entry points of the fused predictor (nm: the viscosity mode).
-// nu_arr (kNu3Array) is an input, nut (kNu3Les, may be null) an output.
-static int predictor3d_run(const char *who, int nm, bool zper, const float *u, const float *v, const float *w,
-                           float nu,
-                           const float *nu_arr, float art, double cs, float *u_star, float *v_star, float *w_star,
-                           float *tau, float *nut, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
-                           int use_supg, void *stream) {
+// The entry points of the fused predictor (nm: the viscosity mode).  nu_arr
+// (kNu3Array) is an input, nut (kNu3Les, may be null) an output.  buoy: the
+// buoyant form (buoyancy3d.hip's entry points; scalar and LES only), null for
+// the plain one -- the same dispatch either way.
+int cfd::predictor3d_run(const char *who, int nm, bool zper, const float *u, const float *v, const float *w,
+                         float nu, const float *nu_arr, float art, double cs, float *u_star, float *v_star,
+                         float *w_star, float *tau, float *nut, int nz, int ny, int nx, double dx, double dy,
+                         double dz, float dt, int use_supg, void *stream, const Pred3Buoy *buoy) {
     CFD_REQUIRE(u && v && w && u_star && v_star && w_star && (nm != kNu3Array || nu_arr), "%s: null pointer", who);
+    CFD_REQUIRE(!buoy || (buoy->T && nm != kNu3Array), "%s: null pointer: T", who);
     CFD_SHAPE3D(who, nz, ny, nx);
-    const float *in[4] = {u, v, w, nu_arr};
+    const float *T = buoy ? buoy->T : nullptr;
+    const float *in[5] = {u, v, w, nu_arr, T};
     float *out[5] = {u_star, v_star, w_star, tau, nut};
     for (int o = 0; o < 5; ++o) {
         if (!out[o]) continue;
-        for (int q = 0; q < 4; ++q) CFD_REQUIRE(out[o] != in[q], "%s: outputs must not alias inputs", who);
+        for (int q = 0; q < 5; ++q) CFD_REQUIRE(out[o] != in[q], "%s: outputs must not alias inputs", who);
         for (int p = 0; p < o; ++p) CFD_REQUIRE(out[o] != out[p], "%s: outputs must not alias each other", who);
     }
     const PredK3 k = make_pred_k3(dx, dy, dz);
@@ -488,7 +508,7 @@ static int predictor3d_run(const char *who, int nm, bool zper, const float *u, c
         const uintptr_t m = (uintptr_t)(4 * c - 1);
         auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
         return nx % c == 0 && al(u) && al(v) && al(w) && al(u_star) && al(v_star) && al(w_star) && al(tau) &&
-               al(nu_arr) && al(nut);
+               al(nu_arr) && al(nut) && al(T);
     };
     while (vec > 1 && !fits(vec)) vec /= 2;
     // the march runs where a plane's byte offsets fit its buffer resource and
@@ -521,8 +541,14 @@ static int predictor3d_run(const char *who, int nm, bool zper, const float *u, c
         a.nut = nut;
         a.c2 = c2;
         a.art = art;
+        a.T = T;
+        a.bx = buoy ? buoy->bx : 0.0f;
+        a.by = buoy ? buoy->by : 0.0f;
+        a.bz = buoy ? buoy->bz : 0.0f;
+        a.t_ref = buoy ? buoy->t_ref : 0.0f;
         const int rows = tuning().pred3_rows ? tuning().pred3_rows : 2;
-        CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, nm, vec, rows, 0, s, zper));
+        if (buoy) CFD_CHECK_HIP(pred_planes_launch_buoyant(a, use_supg != 0, nm, vec, rows, s, zper));
+        else CFD_CHECK_HIP(pred_planes_launch(a, use_supg != 0, nm, vec, rows, 0, s, zper));
         g_last_pred3[0] = 1;
         g_last_pred3[1] = vec;
     } else {
@@ -531,7 +557,19 @@ static int predictor3d_run(const char *who, int nm, bool zper, const float *u, c
 #define CFD_PRED3_CELL(KERNEL, ...)                                                                        \
     hipLaunchKernelGGL(KERNEL, g, dim3(256), 0, s, u, v, w, nu, u_star, v_star, w_star, tau, nz, ny, nx, dt, k, \
                        ##__VA_ARGS__)
-        if (zper && nm == kNu3Les) {
+        if (buoy && zper && nm == kNu3Les) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, true, Pred3Nu, Pred3Buoy>), m, *buoy);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, true, Pred3Nu, Pred3Buoy>), m, *buoy);
+        } else if (buoy && zper) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar, true, Pred3Buoy>), *buoy);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar, true, Pred3Buoy>), *buoy);
+        } else if (buoy && nm == kNu3Les) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, false, Pred3Nu, Pred3Buoy>), m, *buoy);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, false, Pred3Nu, Pred3Buoy>), m, *buoy);
+        } else if (buoy) {
+            if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Scalar, false, Pred3Buoy>), *buoy);
+            else CFD_PRED3_CELL((k_predictor3d<false, kNu3Scalar, false, Pred3Buoy>), *buoy);
+        } else if (zper && nm == kNu3Les) {
             if (use_supg) CFD_PRED3_CELL((k_predictor3d<true, kNu3Les, true, Pred3Nu>), m);
             else CFD_PRED3_CELL((k_predictor3d<false, kNu3Les, true, Pred3Nu>), m);
         } else if (zper) {
@@ -555,6 +593,8 @@ static int predictor3d_run(const char *who, int nm, bool zper, const float *u, c
     CFD_LAUNCH_CHECK();
     return CFD_OK;
 }
+
+extern "C" {
 
 int cfd_predictor3d_f32(const float *u, const float *v, const float *w, float nu_eff, float *u_star,
                         float *v_star, float *w_star, float *tau, int nz, int ny, int nx, double dx, double dy,

@@ -114,6 +114,20 @@ inline unsigned long long persist_poll_ticks() {
 int jacobi2d_persist_solve(float *phi, const float *src, bool pre, const uint8_t *mask, int ny, int nx,
                            float dx2, float dtv, int iterations, hipStream_t s, int *rc, bool zero = false);
 
+// fields3d.hip: the fused 3-D predictor's checks and dispatch (cells per lane,
+// march or per cell, the tuning knobs, the last-path record), shared by the
+// plain entry points and the buoyant ones (buoyancy3d.hip: buoy non-null,
+// nm kNu3Scalar or kNu3Les)
+struct Pred3Args;
+struct Pred3Buoy;
+int predictor3d_run(const char *who, int nm, bool zper, const float *u, const float *v, const float *w, float nu,
+                    const float *nu_arr, float art, double cs, float *u_star, float *v_star, float *w_star,
+                    float *tau, float *nut, int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                    int use_supg, void *stream, const Pred3Buoy *buoy = nullptr);
+// buoyancy3d.hip: pred_planes_launch of the buoyant instantiations (auto chunk)
+hipError_t pred_planes_launch_buoyant(const Pred3Args &a, bool supg, int nm, int vec, int rows, hipStream_t s,
+                                      bool zper);
+
 // poisson3d.hip
 int launch_fix_faces3d(const float *src, float *dst, const uint8_t *mask, int ny, int nx, int za,
                        int zb, int full_lo, int full_hi, hipStream_t s);

@@ -42,6 +42,13 @@
 // its D, the last chunk loads plane 0 as its U -- while the chunk-window test
 // stays on the unwrapped index.  A template parameter: the non-periodic
 // instantiations are the code they were.
+//
+// BUOY (Boussinesq buoyancy): f* gains dt * (b_f * (T_C - t_ref)) on the cells
+// pred3_cell updates, with T_C the cell's own temperature: the R own rows of
+// plane k of T, loaded one plane ahead, no halo -- kNu3Array's pattern, one
+// more 4-byte read per cell.  Scalar and LES viscosity only (the solver has no
+// array-nu step).  A template parameter: the instantiations without it are
+// the code they were; the buoyant ones live in buoyancy3d.hip.
 #pragma once
 #include "common.hpp"
 #include "pred_rows.hpp"
@@ -164,6 +171,15 @@ struct Pred3Args {
     const float *nu_arr;
     float *nut;
     float c2, art;
+    // BUOY: f* += dt * (b_f * (T - t_ref)) on the interior; T: the step's incoming temperature
+    const float *T;
+    float bx, by, bz, t_ref;
+};
+
+// the buoyant term's arguments as the per-cell kernel and the launchers take them
+struct Pred3Buoy {
+    const float *T;
+    float bx, by, bz, t_ref;
 };
 
 // rows j0 - 1 .. j0 + R of one plane of one field (index 0 = row j0 - 1) and
@@ -174,9 +190,10 @@ struct Plane {
     float halo[R];
 };
 
-template <int VEC, int R, bool SUPG, int NM = kNu3Scalar, bool ZPER = false>
+template <int VEC, int R, bool SUPG, int NM = kNu3Scalar, bool ZPER = false, bool BUOY = false>
 __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
     static_assert(!ZPER || NM != kNu3Array, "periodic z: scalar and LES viscosity only");
+    static_assert(!BUOY || NM != kNu3Array, "buoyancy: scalar and LES viscosity only");
     constexpr int SW = 64 * VEC;  // segment width (columns)
     const int lane = threadIdx.x & (kWave - 1);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -249,12 +266,26 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) Nc[r] = pldv<float, VEC>(rn, ro[r + 1]);
     }
+    // BUOY: the R own rows of T, one plane ahead (no halo)
+    [[maybe_unused]] Cells<float, VEC> Tc[R];
+    if constexpr (BUOY) {
+        const __amdgpu_buffer_rsrc_t rt0 = prsrc(a.T, z0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) Tc[r] = pldv<float, VEC>(rt0, ro[r + 1]);
+    }
     for (int z = z0; z < z1; ++z) {
         [[maybe_unused]] Cells<float, VEC> Nn[R];
         if constexpr (NM == kNu3Array) {
             const __amdgpu_buffer_rsrc_t rn = prsrc(a.nu_arr, z + 1 < z1 ? z + 1 : -1);
 #pragma unroll
             for (int r = 0; r < R; ++r) Nn[r] = pldv<float, VEC>(rn, ro[r + 1]);
+        }
+        [[maybe_unused]] Cells<float, VEC> Tn[R];
+        if constexpr (BUOY) {
+            // no plane past the chunk: z1 + 1 is outside the window, periodic or not
+            const __amdgpu_buffer_rsrc_t rtn = prsrc(a.T, z + 1 < z1 ? z + 1 : z1 + 1);
+#pragma unroll
+            for (int r = 0; r < R; ++r) Tn[r] = pldv<float, VEC>(rtn, ro[r + 1]);
         }
         // two planes ahead
         const Plane<VEC, R> Un = load_plane(a.u, z + 2), Vn = load_plane(a.v, z + 2), Wn = load_plane(a.w, z + 2);
@@ -310,9 +341,15 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
                     }
                     float t = 0.0f;
                     if constexpr (SUPG) t = pred3_tau(uc[c], vc[c], wc[c], ne, dt, a.k);
-                    const float nu_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fu, t, ne, dt, a.k);
-                    const float nv_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fv, t, ne, dt, a.k);
-                    const float nw_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fw, t, ne, dt, a.k);
+                    float nu_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fu, t, ne, dt, a.k);
+                    float nv_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fv, t, ne, dt, a.k);
+                    float nw_ = pred3_cell<SUPG>(uc[c], vc[c], wc[c], fw, t, ne, dt, a.k);
+                    if constexpr (BUOY) {
+                        const float th = Tc[r].x[c] - a.t_ref;
+                        nu_ = nu_ + dt * (a.bx * th);
+                        nv_ = nv_ + dt * (a.by * th);
+                        nw_ = nw_ + dt * (a.bz * th);
+                    }
                     uo.x[c] = in ? nu_ : uc[c];
                     vo.x[c] = in ? nv_ : vc[c];
                     wo.x[c] = in ? nw_ : wc[c];
@@ -343,39 +380,46 @@ __global__ __launch_bounds__(256) void k_predictor3d_planes(Pred3Args a) {
 #pragma unroll
             for (int r = 0; r < R; ++r) Nc[r] = Nn[r];
         }
+        if constexpr (BUOY) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) Tc[r] = Tn[r];
+        }
     }
 }
 
-template <int VEC, int R, int NM, bool ZPER = false>
+template <int VEC, int R, int NM, bool ZPER = false, bool BUOY = false>
 inline const void *pred_planes_kernel_nm(bool supg) {
-    return supg ? (const void *)k_predictor3d_planes<VEC, R, true, NM, ZPER>
-                : (const void *)k_predictor3d_planes<VEC, R, false, NM, ZPER>;
+    return supg ? (const void *)k_predictor3d_planes<VEC, R, true, NM, ZPER, BUOY>
+                : (const void *)k_predictor3d_planes<VEC, R, false, NM, ZPER, BUOY>;
 }
-template <int VEC, int R>
+template <int VEC, int R, bool BUOY = false>
 inline const void *pred_planes_kernel(bool supg, int nm, bool zper) {
     if (zper)  // scalar and LES only (the caller has no periodic array mode)
-        return nm == kNu3Les ? pred_planes_kernel_nm<VEC, R, kNu3Les, true>(supg)
-                             : pred_planes_kernel_nm<VEC, R, kNu3Scalar, true>(supg);
-    if (nm == kNu3Array) return pred_planes_kernel_nm<VEC, R, kNu3Array>(supg);
-    if (nm == kNu3Les) return pred_planes_kernel_nm<VEC, R, kNu3Les>(supg);
-    return pred_planes_kernel_nm<VEC, R, kNu3Scalar>(supg);
+        return nm == kNu3Les ? pred_planes_kernel_nm<VEC, R, kNu3Les, true, BUOY>(supg)
+                             : pred_planes_kernel_nm<VEC, R, kNu3Scalar, true, BUOY>(supg);
+    if constexpr (!BUOY)  // no buoyant array mode either
+        if (nm == kNu3Array) return pred_planes_kernel_nm<VEC, R, kNu3Array>(supg);
+    if (nm == kNu3Les) return pred_planes_kernel_nm<VEC, R, kNu3Les, false, BUOY>(supg);
+    return pred_planes_kernel_nm<VEC, R, kNu3Scalar, false, BUOY>(supg);
 }
 
 // Plane-march launch: cells per lane vec (1, 2, 4), rows per wave rows (1, 2),
 // planes per chunk zchunk (0: auto), zper: periodic z (not with kNu3Array);
 // a.nseg / a.ntile / a.zchunk are filled here.  The caller has checked shape
-// (a plane below 2^31 bytes, nx % vec == 0) and alignment.
+// (a plane below 2^31 bytes, nx % vec == 0) and alignment.  BUOY: the buoyant
+// instantiations (a.T, a.bx .. a.t_ref set; not with kNu3Array).
+template <bool BUOY = false>
 inline hipError_t pred_planes_launch(Pred3Args a, bool supg, int nm, int vec, int rows, int zchunk, hipStream_t s,
                                      bool zper = false) {
     const void *f;
     if (rows == 1)
-        f = vec == 4   ? pred_planes_kernel<4, 1>(supg, nm, zper)
-            : vec == 2 ? pred_planes_kernel<2, 1>(supg, nm, zper)
-                       : pred_planes_kernel<1, 1>(supg, nm, zper);
+        f = vec == 4   ? pred_planes_kernel<4, 1, BUOY>(supg, nm, zper)
+            : vec == 2 ? pred_planes_kernel<2, 1, BUOY>(supg, nm, zper)
+                       : pred_planes_kernel<1, 1, BUOY>(supg, nm, zper);
     else
-        f = vec == 4   ? pred_planes_kernel<4, 2>(supg, nm, zper)
-            : vec == 2 ? pred_planes_kernel<2, 2>(supg, nm, zper)
-                       : pred_planes_kernel<1, 2>(supg, nm, zper);
+        f = vec == 4   ? pred_planes_kernel<4, 2, BUOY>(supg, nm, zper)
+            : vec == 2 ? pred_planes_kernel<2, 2, BUOY>(supg, nm, zper)
+                       : pred_planes_kernel<1, 2, BUOY>(supg, nm, zper);
     a.nseg = ceil_div(a.nx, 64 * vec);
     a.ntile = ceil_div(a.ny, 4 * rows);
     // planes per chunk: each chunk re-reads 2 planes, so long chunks, but at

@@ -449,8 +449,16 @@ def _fields3d(model, /, **others):
     return shape
 
 
+def _buoyancy_args(who, buoyancy, t_ref):
+    """(bx, by, bz, t_ref) as Python floats of float32 values for the buoyant
+    predictor entry points."""
+    if buoyancy is None or len(buoyancy) != 3:
+        raise ValueError(f"{who}: with T, buoyancy is the three float32 coefficients (bx, by, bz)")
+    return tuple(float(np.float32(b)) for b in buoyancy) + (float(np.float32(t_ref)),)
+
+
 def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=None, v_star=None, w_star=None,
-                      tau=None, store_tau=True, periodic_z=False):
+                      tau=None, store_tau=True, periodic_z=False, T=None, buoyancy=None, t_ref=0.0):
     """The 3-D fused predictor (cfd_predictor3d_f32): SUPG tau, convection and
     Laplacian of u, v, w and f_star = f + dt*(-conv + lap) in one pass, the six
     faces copied through.  ``nu_eff`` is a scalar, or a tensor of the fields'
@@ -459,12 +467,25 @@ def predictor3d_fused(u, v, w, dx, dy, dz, dt, nu_eff, use_supg=True, u_star=Non
     ``tau`` given: tau is not stored (24 B per cell instead of 28) and None is
     returned for it.  Without SUPG a stored tau is zeros.  ``periodic_z``:
     every plane is interior in z and plane nz-1's U neighbour is plane 0
-    (cfd_predictor3d_zper_f32; scalar ``nu_eff`` only)."""
+    (cfd_predictor3d_zper_f32; scalar ``nu_eff`` only).  ``T`` (a tensor of the
+    fields' shape; scalar ``nu_eff`` only): Boussinesq buoyancy, the interior
+    cells' f_star gains dt * (b_f * (T - t_ref)) in float32 with ``buoyancy`` =
+    (bx, by, bz) (cfd_predictor3d_buoy_f32 / _buoy_zper_f32); without ``T``
+    the calls are the plain ones."""
     us = torch.empty_like(u) if u_star is None else u_star
     vs = torch.empty_like(u) if v_star is None else v_star
     ws = torch.empty_like(u) if w_star is None else w_star
     if tau is None and store_tau:
         tau = torch.empty_like(u)
+    if T is not None:
+        if isinstance(nu_eff, torch.Tensor) and nu_eff.dim() > 0:
+            raise ValueError("predictor3d_fused: buoyancy (T) takes a scalar nu_eff (LES: predictor3d_fused_les)")
+        b = _buoyancy_args("predictor3d_fused", buoyancy, t_ref)
+        nz, ny, nx = _fields3d(u, v=v, w=w, T=T, u_star=us, v_star=vs, w_star=ws, tau=tau)
+        call("cfd_predictor3d_buoy_zper_f32" if periodic_z else "cfd_predictor3d_buoy_f32", ptr(u), ptr(v), ptr(w),
+             ptr(T), float(np.float32(nu_eff)), *b, ptr(us), ptr(vs), ptr(ws), ptr(tau), nz, ny, nx, float(dx),
+             float(dy), float(dz), _dt_arg(dt, u.dtype), int(bool(use_supg)), stream_handle())
+        return us, vs, ws, tau
     if isinstance(nu_eff, torch.Tensor) and nu_eff.dim() > 0:
         if periodic_z:
             raise ValueError("predictor3d_fused: periodic_z takes a scalar nu_eff (LES: predictor3d_fused_les)")
@@ -495,7 +516,8 @@ def compute_smagorinsky_viscosity3d(u, v, w, dx, dy, dz, cs, out=None):
 
 
 def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=True, u_star=None, v_star=None,
-                          w_star=None, tau=None, nu_t=None, store_tau=True, store_nu_t=True, periodic_z=False):
+                          w_star=None, tau=None, nu_t=None, store_tau=True, store_nu_t=True, periodic_z=False,
+                          T=None, buoyancy=None, t_ref=0.0):
     """The 3-D LES predictor (cfd_predictor3d_les_f32) in one pass: nu_t =
     compute_smagorinsky_viscosity3d(u, v, w, ...), nu_eff = (nu + nu_t) +
     art_visc per cell in float32, then predictor3d_fused with that array --
@@ -503,7 +525,10 @@ def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=Tr
     holds anyway.  Returns (u_star, v_star, w_star, tau, nu_t); arrays not
     given are allocated, unless ``store_tau`` / ``store_nu_t`` is False: that
     array is then not stored and None is returned for it.  ``periodic_z``: as
-    in predictor3d_fused (cfd_predictor3d_les_zper_f32; nu_t on all planes)."""
+    in predictor3d_fused (cfd_predictor3d_les_zper_f32; nu_t on all planes).
+    ``T``, ``buoyancy``, ``t_ref``: Boussinesq buoyancy as in predictor3d_fused
+    (cfd_predictor3d_les_buoy_f32 / _les_buoy_zper_f32); tau and nu_t are
+    what they are without it."""
     us = torch.empty_like(u) if u_star is None else u_star
     vs = torch.empty_like(u) if v_star is None else v_star
     ws = torch.empty_like(u) if w_star is None else w_star
@@ -511,6 +536,14 @@ def predictor3d_fused_les(u, v, w, dx, dy, dz, dt, nu, art_visc, cs, use_supg=Tr
         tau = torch.empty_like(u)
     if nu_t is None and store_nu_t:
         nu_t = torch.empty_like(u)
+    if T is not None:
+        b = _buoyancy_args("predictor3d_fused_les", buoyancy, t_ref)
+        nz, ny, nx = _fields3d(u, v=v, w=w, T=T, u_star=us, v_star=vs, w_star=ws, tau=tau, nu_t=nu_t)
+        call("cfd_predictor3d_les_buoy_zper_f32" if periodic_z else "cfd_predictor3d_les_buoy_f32", ptr(u), ptr(v),
+             ptr(w), ptr(T), float(np.float32(nu)), float(np.float32(art_visc)), float(cs), *b, ptr(us), ptr(vs),
+             ptr(ws), ptr(tau), ptr(nu_t), nz, ny, nx, float(dx), float(dy), float(dz), _dt_arg(dt, u.dtype),
+             int(bool(use_supg)), stream_handle())
+        return us, vs, ws, tau, nu_t
     nz, ny, nx = _fields3d(u, v=v, w=w, u_star=us, v_star=vs, w_star=ws, tau=tau, nu_t=nu_t)
     call("cfd_predictor3d_les_zper_f32" if periodic_z else "cfd_predictor3d_les_f32", ptr(u), ptr(v), ptr(w),
          float(np.float32(nu)), float(np.float32(art_visc)),

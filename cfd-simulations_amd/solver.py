@@ -731,6 +731,11 @@ class LidDrivenCavity3DSolver:
         """Stages that read the step's incoming u, v, w (and nu_t) before the
         projection overwrites them: none here (the cylinder channel's scalar)."""
 
+    def _predictor_buoyancy(self):
+        """Further keyword arguments of the step's predictor call: none here
+        (the cylinder channel's buoyancy: T, buoyancy, t_ref)."""
+        return {}
+
     @property
     def energy_history(self):
         """[(step, mean kinetic energy)], read lazily from the device."""
@@ -769,13 +774,13 @@ class LidDrivenCavity3DSolver:
             K.predictor3d_fused_les(self.u, self.v, self.w, *sp, dt, cfg.nu, cfg.artificial_viscosity,
                                     cfg.smagorinsky_constant, cfg.use_supg, u_star=self.u_star,
                                     v_star=self.v_star, w_star=self.w_star, nu_t=self.nu_t, store_tau=False,
-                                    periodic_z=self._periodic_z)
+                                    periodic_z=self._periodic_z, **self._predictor_buoyancy())
         else:
             # nu_eff = (nu + 0) + art_visc in float32, a scalar
             nu_eff = np.float32(np.float32(cfg.nu) + np.float32(0.0)) + np.float32(cfg.artificial_viscosity)
             K.predictor3d_fused(self.u, self.v, self.w, *sp, dt, nu_eff, cfg.use_supg, u_star=self.u_star,
                                 v_star=self.v_star, w_star=self.w_star, store_tau=False,
-                                periodic_z=self._periodic_z)
+                                periodic_z=self._periodic_z, **self._predictor_buoyancy())
         self._after_predictor(dt)
         self.apply_boundary_conditions(self.u_star, self.v_star, self.w_star)
         K.compute_divergence3d(self.u_star, self.v_star, self.w_star, *sp, out=self.div_u_star,
@@ -1026,9 +1031,30 @@ class CylinderChannel3DConfig(OptimizedTurbulentConfig):
     turbulent_prandtl: float = 0.85
     scalar_inlet: float = 0.0
     scalar_cylinder: float = 1.0
+    # Boussinesq buoyancy (needs the scalar): off at richardson = 0.  Ri =
+    # g beta dT D / V_inf^2 with dT = scalar_cylinder - scalar_inlet and D =
+    # 2 R_cylinder; gravity_direction is g's direction in (x, y, z), any
+    # non-zero length; T - scalar_reference (None: scalar_inlet) drives the
+    # term, and hot fluid is pushed against g
+    richardson: float = 0.0
+    gravity_direction: tuple = (0.0, -1.0, 0.0)
+    scalar_reference: float | None = None
 
     def __post_init__(self):
         super().__post_init__()
+        if self.richardson != 0:
+            if not self.scalar:
+                raise ValueError("CylinderChannel3DConfig: richardson != 0 needs the scalar (scalar=True)")
+            if self.scalar_cylinder == self.scalar_inlet:
+                raise ValueError("CylinderChannel3DConfig: richardson != 0 needs scalar_cylinder != scalar_inlet "
+                                 "(the temperature scale of the Richardson number)")
+            try:
+                g = [float(x) for x in self.gravity_direction]
+            except (TypeError, ValueError):
+                g = []
+            if len(g) != 3 or not all(np.isfinite(g)) or not any(x != 0.0 for x in g):
+                raise ValueError(f"CylinderChannel3DConfig: gravity_direction must be three finite numbers of "
+                                 f"non-zero norm (got {self.gravity_direction!r})")
         if not (self.prandtl > 0.0 and self.turbulent_prandtl > 0.0):
             raise ValueError(f"CylinderChannel3DConfig: prandtl and turbulent_prandtl must be positive "
                              f"(got {self.prandtl}, {self.turbulent_prandtl})")
@@ -1113,16 +1139,26 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
     the artificial viscosity is not added) into a second buffer, the two swap,
     and K.apply_scalar_bc_heat3d relaxes T towards scalar_cylinder in the
     forcing zone with the step's force_strength and sets the faces (inlet
-    scalar_inlet; outlet, adiabatic walls and spanwise faces copy).  The
-    scalar never acts back on the flow.  ``heat_history`` and
+    scalar_inlet; outlet, adiabatic walls and spanwise faces copy).  Without
+    buoyancy the scalar never acts back on the flow.  ``heat_history`` and
     ``nusselt_numbers()`` read the per-step heat sums lazily; snapshots gain
     T; tests/scalar3d_reference.py states the arithmetic.
+
+    Buoyancy (config.richardson != 0, with the scalar; off by default, and
+    then every launch is what it was): the predictor adds dt * (b_f * (T -
+    t_ref)) in float32 to the interior cells' u*, v*, w*, inside its own
+    kernel, with the step's incoming T, ``buoyancy_vector`` b = f32(-Ri
+    V_inf^2 / (2 R_cylinder (scalar_cylinder - scalar_inlet)) g / |g|) and
+    t_ref = f32(scalar_reference, else scalar_inlet): hot fluid is pushed
+    against gravity_direction.  Snapshots need nothing new (T is stored), and
+    the adaptive dt does not look at the buoyant acceleration;
+    tests/buoyancy3d_reference.py states the arithmetic.
 
     Not yet: temporal blocking of the masked 3-D Jacobi (with a mask it runs
     single sweeps: DESIGN.md 4.4), a periodic form of that Jacobi, masks that
     vary along z in the fused GS, pressure statistics (the step keeps no p), a
-    Strouhal estimate from the lift history, buoyancy, float64 and the slab
-    path."""
+    Strouhal estimate from the lift history, the scalar's advance fused into
+    the predictor's march, float64 and the slab path."""
 
     _stats_span_default = True
 
@@ -1168,6 +1204,22 @@ class CylinderChannel3DSolver(LidDrivenCavity3DSolver):
             # alpha = f32(nu / Pr), 1 / Pr_t = f32(1 / Pr_t): formed in double, rounded once
             self._alpha = np.float32(float(cfg.nu) / cfg.prandtl)
             self._inv_prt = np.float32(1.0 / cfg.turbulent_prandtl)
+        if cfg.richardson != 0:
+            # b_i = f32(-Ri V_inf^2 / (D dT) g_i / |g|): formed in double, rounded once per component
+            dT = cfg.scalar_cylinder - cfg.scalar_inlet
+            k = -cfg.richardson * cfg.V_inf ** 2 / (2.0 * cfg.R_cylinder * dT)
+            gx, gy, gz = (float(x) for x in cfg.gravity_direction)
+            n = np.sqrt(gx * gx + gy * gy + gz * gz)
+            self.buoyancy_vector = tuple(np.float32(k * (g / n)) for g in (gx, gy, gz))
+            self._t_ref = np.float32(cfg.scalar_inlet if cfg.scalar_reference is None else cfg.scalar_reference)
+
+    def _predictor_buoyancy(self):
+        """With richardson != 0 the predictor adds dt * (b_f * (T - t_ref)) to
+        the interior cells' u*, v*, w* with the step's incoming T (the
+        predictor runs before _after_predictor swaps T)."""
+        if self.config.richardson == 0:
+            return {}
+        return {"T": self.T, "buoyancy": self.buoyancy_vector, "t_ref": self._t_ref}
 
     def _heat_slot(self):
         k = len(self._energy_steps)

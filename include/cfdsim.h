@@ -462,6 +462,42 @@ int cfd_predictor3d_les_zper_f32(const float *u, const float *v, const float *w,
                                  float *w_star, float *tau, float *nu_t, int nz, int ny, int nx,
                                  double dx, double dy, double dz, float dt, int use_supg,
                                  void *stream);
+/* cfd_predictor3d_f32 and cfd_predictor3d_les_f32 with Boussinesq buoyancy, and
+ * their periodic-z forms (the pad rule of cfd_predictor3d_zper_f32, T padded
+ * like the fields): on every cell the plain predictor updates,
+ *   f_star = p + dt * (b_f * (T - t_ref)),   (b_u, b_v, b_w) = (bx, by, bz),
+ * with p the plain predictor's value of that cell and T the cell's own
+ * temperature -- float32 operations in this order, nothing fused; the face
+ * cells keep f; tau and nu_t are the plain predictor's.  b = (0, 0, 0) or
+ * T == t_ref everywhere gives the plain predictor's values (a -0.0 may become
+ * +0.0).  T is an input of the fields' shape: NULL is refused, and it must not
+ * alias an output.  The term is part of both predictor kernels (one more
+ * 4-byte read per cell: the plane march keeps its own rows of T one plane
+ * ahead, no halo), so cfd_set_predictor3d_config and
+ * cfd_get_last_predictor3d_path apply as to the plain launches, T's alignment
+ * included in the cells-per-lane rule.  28 B per cell with tau not stored. */
+int cfd_predictor3d_buoy_f32(const float *u, const float *v, const float *w, const float *T,
+                             float nu_eff, float bx, float by, float bz, float t_ref,
+                             float *u_star, float *v_star, float *w_star, float *tau,
+                             int nz, int ny, int nx, double dx, double dy, double dz, float dt,
+                             int use_supg, void *stream);
+int cfd_predictor3d_les_buoy_f32(const float *u, const float *v, const float *w, const float *T,
+                                 float nu, float art_visc, double cs, float bx, float by,
+                                 float bz, float t_ref, float *u_star, float *v_star,
+                                 float *w_star, float *tau, float *nu_t, int nz, int ny, int nx,
+                                 double dx, double dy, double dz, float dt, int use_supg,
+                                 void *stream);
+int cfd_predictor3d_buoy_zper_f32(const float *u, const float *v, const float *w, const float *T,
+                                  float nu_eff, float bx, float by, float bz, float t_ref,
+                                  float *u_star, float *v_star, float *w_star, float *tau,
+                                  int nz, int ny, int nx, double dx, double dy, double dz,
+                                  float dt, int use_supg, void *stream);
+int cfd_predictor3d_les_buoy_zper_f32(const float *u, const float *v, const float *w,
+                                      const float *T, float nu, float art_visc, double cs,
+                                      float bx, float by, float bz, float t_ref, float *u_star,
+                                      float *v_star, float *w_star, float *tau, float *nu_t,
+                                      int nz, int ny, int nx, double dx, double dy, double dz,
+                                      float dt, int use_supg, void *stream);
 /* Kernel of cfd_predictor3d_f32 / _nu_f32 / _les_f32 (tuning, per host
  * thread; the same bits either way; cfd_reset_tuning restores auto):
  * variant 0 = auto (the plane march --

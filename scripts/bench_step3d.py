@@ -63,6 +63,16 @@ stage, all alternating window by window (the advance at its algorithmic 20 B
 per cell, 24 B with nu_t); then CylinderChannel3DSolver.time_step with the
 scalar off and on, the two solvers alternating.
 
+--buoyancy: the Boussinesq buoyancy leg instead, at the same
+grid: the buoyant predictor (cfd_predictor3d_buoy_f32 and its LES / periodic
+forms, 28 B per cell against the plain predictor's 24; 32 against 28 with LES)
+beside the plain one on the same fields, SUPG and upwind, scalar nu and LES,
+flat and periodic, and the two-launch alternative (the plain predictor, then
+torch passes that add the term to v*), all alternating window by window, with
+each pair's ratio next to the byte model's; then
+CylinderChannel3DSolver.time_step with scalar=True at richardson 0 and 1, the
+two solvers alternating.
+
 The script sets no time limits itself.  To give every GPU stage a limit of its
 own, run one invocation per stage, each under `timeout` and chained with &&:
 `--les --sizes 512 --no-step`, `--les --sizes 1024 --no-step --check`, then
@@ -750,6 +760,138 @@ def scalar_leg(rounds, launches, steps, step_only=False):
                           "energy_last": sv.energy_history[-1][1]}), flush=True)
 
 
+def buoyancy_leg(rounds, launches, steps, step_only=False):
+    """Boussinesq buoyancy at the default 600 x 180 x 120 grid:
+    the buoyant predictor beside the plain one on the same fields -- SUPG and
+    upwind, scalar nu and LES, flat and periodic -- and the two-launch
+    alternative (the plain predictor, then a torch add_ of the term on v*),
+    all alternating window by window; then CylinderChannel3DSolver.time_step
+    with scalar=True at richardson 0 and 1, the two solvers alternating."""
+    from cfd_simulations_amd.solver import CylinderChannel3DConfig, CylinderChannel3DSolver
+    c = CylinderChannel3DConfig()
+    nz, ny, nx = c.nz, c.ny, c.nx
+    cells = nz * ny * nx
+    grid = [nz, ny, nx]
+    if not step_only:
+        s = CylinderChannel3DSolver(CylinderChannel3DConfig(use_les=True, spanwise_perturbation=0.05, scalar=True,
+                                                            richardson=1.0))
+        for _ in range(2):
+            s.time_step()   # fields that depend on z and a heated T
+        stars = [torch.empty_like(s.u) for _ in range(3)]
+        nu_t = torch.empty_like(s.u)
+        theta = torch.empty_like(s.u)
+        b, t_ref = s.buoyancy_vector, s._t_ref
+        o = dict(u_star=stars[0], v_star=stars[1], w_star=stars[2], store_tau=False)
+        paths = {}
+
+        def pred(label, supg, les, per, buoy, config=(0, 0, 0)):
+            kw = dict(T=s.T, buoyancy=b, t_ref=t_ref) if buoy else {}
+
+            def fn():
+                call("cfd_set_predictor3d_config", *config)
+                if les:
+                    K.predictor3d_fused_les(s.u, s.v, s.w, c.dx, c.dy, c.dz, DT, c.nu, c.artificial_viscosity,
+                                            c.smagorinsky_constant, supg, nu_t=nu_t, periodic_z=per, **o, **kw)
+                else:
+                    K.predictor3d_fused(s.u, s.v, s.w, c.dx, c.dy, c.dz, DT, NU, supg, periodic_z=per, **o, **kw)
+                paths[label] = last_path()
+            return fn
+
+        def two_launch(plain):
+            def fn():   # the term on v* as a second pass: theta = T - t_ref, v* += (dt by) theta
+                plain()
+                torch.sub(s.T, float(t_ref), out=theta)
+                stars[1].add_(theta, alpha=float(DT) * float(b[1]))
+            return fn
+
+        def two_launch_one_pass(plain):
+            def fn():   # the cheapest second pass torch offers: v* += (dt by) T (the constant left out)
+                plain()
+                stars[1].add_(s.T, alpha=float(DT) * float(b[1]))
+            return fn
+
+        cases = {}
+        for supg in (True, False):
+            for les in (False, True):
+                for per in (False, True):
+                    tag = ("supg" if supg else "upwind") + ("_les" if les else "") + ("_zper" if per else "")
+                    nb = 28 if les else 24   # nu_t stored with LES
+                    cases[f"plain_{tag}"] = (pred(f"plain_{tag}", supg, les, per, False), nb * cells)
+                    cases[f"buoyant_{tag}"] = (pred(f"buoyant_{tag}", supg, les, per, True), (nb + 4) * cells)
+        cases["two_launch_supg"] = (two_launch(cases["plain_supg"][0]), (24 + 8 + 12) * cells)
+        cases["two_launch_one_pass_supg"] = (two_launch_one_pass(cases["plain_supg"][0]), (24 + 12) * cells)
+        # every march shape of the buoyant LES kernels (where the registers of T show: DESIGN.md 4.7)
+        for supg in (True, False):
+            for r, cpl in MARCH_SHAPES:
+                k = f"buoyant_{'supg' if supg else 'upwind'}_les_r{r}_c{cpl}"
+                cases[k] = (pred(k, supg, True, False, True, (2, r, cpl)), 32 * cells)
+        ms = {k: [] for k in cases}
+        try:
+            for fn, _ in cases.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for k, (fn, _) in cases.items():
+                    ms[k].append(window_ms(fn, launches))
+        finally:
+            call("cfd_reset_tuning")
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, v in ms.items():
+            nbytes = cases[k][1]
+            rec = {"bench": "buoyancy3d_kernel", "grid": grid, "kernel": k, "ms": round(med[k], 4),
+                   "ms_min": round(min(v), 4), "ms_max": round(max(v), 4), "windows_ms": [round(x, 4) for x in v],
+                   "rounds": rounds, "launches_per_round": launches, "algorithmic_bytes": nbytes,
+                   "ms_at_hbm_peak": round(nbytes / HBM_PEAK * 1e3, 4),
+                   "hbm_fraction": round(nbytes / (med[k] * 1e-3) / HBM_PEAK, 4)}
+            if k in paths:
+                rec["path"], rec["cells_per_lane"] = paths[k]
+            print(json.dumps(rec), flush=True)
+        for mode in ("supg_les", "upwind_les"):
+            sweep = {k: med[k] for k in cases if k.startswith(f"buoyant_{mode}_r")}
+            best = min(sweep, key=sweep.get)
+            print(json.dumps({"bench": "buoyancy3d_les_shapes", "mode": mode, "fastest": best,
+                              "fastest_ms": round(sweep[best], 4), "auto_ms": round(med[f"buoyant_{mode}"], 4),
+                              "auto_path": paths[f"buoyant_{mode}"], "plain_auto_ms": round(med[f"plain_{mode}"], 4),
+                              "fastest_over_plain_auto": round(sweep[best] / med[f"plain_{mode}"], 3),
+                              "over_plain_auto": {k[len(f"buoyant_{mode}_"):]: round(v / med[f"plain_{mode}"], 3)
+                                                  for k, v in sweep.items()}}), flush=True)
+        for k in [k for k in cases if k.startswith("buoyant_") and f"plain_{k[len('buoyant_'):]}" in cases]:
+            tag = k[len("buoyant_"):]
+            p, q = ms[f"plain_{tag}"], ms[k]
+            rec = {"bench": "buoyancy3d_ratio", "mode": tag, "buoyant_over_plain": round(med[k] / med[f"plain_{tag}"], 3),
+                   "byte_model_ratio": round(cases[k][1] / cases[f"plain_{tag}"][1], 3),
+                   "delta_ms": round(med[k] - med[f"plain_{tag}"], 4),
+                   "window_spread_ms": round(max(max(p) - min(p), max(q) - min(q)), 4)}
+            if tag == "supg":
+                rec["two_launch_over_plain"] = round(med["two_launch_supg"] / med["plain_supg"], 3)
+                rec["two_launch_one_pass_over_plain"] = round(med["two_launch_one_pass_supg"] / med["plain_supg"], 3)
+                rec["buoyant_over_two_launch_one_pass"] = round(med[k] / med["two_launch_one_pass_supg"], 3)
+            print(json.dumps(rec), flush=True)
+        del s, stars, nu_t, theta, cases
+        torch.cuda.empty_cache()
+    solvers = {}
+    for k, ri in (("ri0", 0.0), ("ri1", 1.0)):
+        sv = solvers[k] = CylinderChannel3DSolver(CylinderChannel3DConfig(spanwise_perturbation=0.05, scalar=True,
+                                                                          richardson=ri))
+        for _ in range(2):
+            sv.time_step()
+    torch.cuda.synchronize()
+    st = {k: [] for k in solvers}
+    for _ in range(rounds):
+        for k, sv in solvers.items():
+            st[k].append(window_ms(sv.time_step, steps))
+    med = {k: statistics.median(v) for k, v in st.items()}
+    for k, sv in solvers.items():
+        print(json.dumps({"bench": "buoyancy3d_time_step", "grid": grid, "richardson": sv.config.richardson,
+                          "scalar": True, "les": False, "pressure": "rbgs", "iterations": c.pressure_iterations,
+                          "steps_per_window": steps, "rounds": rounds, "ms_per_step": round(med[k], 3),
+                          "ms_min": round(min(st[k]), 3), "ms_max": round(max(st[k]), 3),
+                          "windows_ms": [round(x, 3) for x in st[k]],
+                          "delta_ms_over_ri0": round(med[k] - med["ri0"], 3),
+                          "energy_last": sv.energy_history[-1][1]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="512,1024")
@@ -768,9 +910,15 @@ def main():
     ap.add_argument("--stats-step-only", action="store_true", help="with --stats: only the five time_step timings")
     ap.add_argument("--scalar", action="store_true", help="the passive scalar leg (see above) and nothing else")
     ap.add_argument("--scalar-step-only", action="store_true", help="with --scalar: only the two time_step timings")
+    ap.add_argument("--buoyancy", action="store_true", help="the buoyancy leg (see above) and nothing else")
+    ap.add_argument("--buoyancy-step-only", action="store_true",
+                    help="with --buoyancy: only the two time_step timings")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_step3d.py needs the GPU")
+    if a.buoyancy:
+        buoyancy_leg(a.rounds, a.launches, 3, a.buoyancy_step_only)
+        return
     if a.scalar:
         scalar_leg(a.rounds, a.launches, 3, a.scalar_step_only)
         return
