@@ -64,7 +64,13 @@ const char *cfd_device_arch(void);
  * Edges keep their values (Dirichlet), except masked edge cells -> 0.
  * resid_every > 0: after every resid_every-th iteration k, max|phi_new - phi|
  * over updated cells is written to resid_out[k/resid_every - 1] (device array
- * of floor(iters/resid_every) elements; an extension, the reference has none). */
+ * of floor(iters/resid_every) elements; an extension, the reference has none).
+ * The maximum is the fold `if (c > m) m = c` from 0 over every cell of the rows
+ * a sweep writes (rows 1 .. ny-2, in 3-D of planes 1 .. nz-2; solid cells
+ * count with |0 - phi|, edge columns change by 0): a NaN change never raises
+ * it, an infinite one does, a sweep whose changes are all NaN gives 0.  The
+ * same holds for cfd_jacobi2d_f64, cfd_jacobi3d_f32 and the resid of
+ * cfd_jacobi3d_sweep_f32 (tests/test_gpu_poisson_edges.py). */
 int cfd_jacobi2d_f32(const float *div, float *phi, float *phi_tmp, float *rhs_ws,
                      const uint8_t *mask, int ny, int nx, double dx, float dt, int iters,
                      int resid_every, float *resid_out, void *stream);
@@ -125,6 +131,21 @@ int cfd_jacobi3d_zero_f32(const float *div, float *phi, float *phi_tmp, float *r
  * use_fast_pressure=True branch, v5.py:330-335): red-black Gauss-Seidel in
  * place on phi; colour 0 = cells with (i+j) odd first; masked cells skipped;
  * stop after the first iteration whose max|change| < tolerance.
+ * The edge rules of that test, on every route (tests/test_gpu_poisson_edges.py):
+ * the comparison is max|change| < (float)tolerance with max|change| folded as
+ * `if (c > m) m = c` from 0 (v5.py:220-225), so
+ *   - a NaN change never counts: a solve with NaN cells stops on its finite
+ *     cells' changes, and an iteration whose changes are all NaN has max 0;
+ *   - an infinite change counts: while a cell turns infinite no tolerance
+ *     below Inf stops the solve;
+ *   - tolerance equal to an iteration's max|change| does not stop at that
+ *     iteration, the next float above it does;
+ *   - a NaN, zero or negative tolerance, or a double that rounds to float 0
+ *     (1e-50), runs every iteration; Inf stops after the first iteration
+ *     unless one of its changes is infinite.
+ * (cfd_rbgs2d_f64 compares in double with the tolerance as passed.)  NaN, Inf,
+ * -0.0 and subnormal cells of phi and div are carried as IEEE arithmetic in the
+ * reference's operation order carries them, solid cells keep theirs.
  * phi_tmp: same-size scratch (optional).  When given (and nx % 4 == 0, 16-byte
  * aligned arrays, blocking not switched off), each iteration runs as ONE fused
  * out-of-place pass over both colours (ping-pong phi/phi_tmp; the result

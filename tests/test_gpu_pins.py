@@ -789,11 +789,16 @@ def test_rbgs2d_persistent_stop_at_every_iteration(ni, masked, mode):
     and 23 iterations on a grid of 3 x 4 .. 5 x 7 tiles.  A stop is seen two
     blocks late (or after the loop, for the last two blocks) and the block it
     fell in is re-run from its input granules; the count and every value must
-    be the oracle's.  Then the same solve with tol = 0 and a stop-free tol."""
+    be the oracle's.  Then the same solve with tol = 0 and a stop-free tol.
+    The row length must be a multiple of 4: other lengths take the in-place
+    colour passes and never reach the persistent kernel.  The kernel's
+    diagnostic trace shows that it ran."""
     call("cfd_set_small2d_gs_iters", ni, 2)
     call("cfd_set_small2d_gs_persistent", mode)
+    trace = torch.zeros(1 << 19, dtype=torch.int64, device=DEV)
+    call("cfd_set_small2d_gs_trace", ptr(trace), trace.numel() * 8)
     rng = np.random.default_rng(70 + ni)
-    div = rng.standard_normal((75, 170)).astype(np.float32) * np.float32(1e-2)
+    div = rng.standard_normal((75, 172)).astype(np.float32) * np.float32(1e-2)
     mask = (rng.random(div.shape) < 0.05) if masked else None
     kw = dict(dx=0.1, dy=0.1, dt=np.float32(1.0), mask=mask)
     _, _, mc = oracle.rbgs2d_maxc(div, iters=23, tol=0.0, **kw)
@@ -824,6 +829,7 @@ def test_rbgs2d_persistent_stop_at_every_iteration(ni, masked, mode):
             K.solve_pressure_gauss_seidel_fast(phi, d, 0.1, 0.1, np.float32(1.0), m, N, tol, iters_done=done)
             assert int(host(done)[0]) == n_ref == N, (tol, N)
             assert np.array_equal(host(phi), ref), (tol, N)
+    assert host(trace).any()  # (the fixture's reset takes the trace buffer away again)
 
 
 def test_rbgs2d_persistent_repeated_solves_reuse_workspace():
