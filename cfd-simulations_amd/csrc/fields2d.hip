@@ -1,264 +1,33 @@
 // fields2d.hip -- predictor (advection-diffusion), divergence, projection,
 // step epilogue and diagnostic reductions of the v5 cylinder solver's
-// time_step(), v5.py:375-441, for gfx950.
+// time_step(), v5.py:375-441, for gfx950, on float32 fields
+// (memory_efficient=True, the reference's configuration).
 //
-// Arithmetic follows the reference as it executes in NumPy-scalar form: every
-// Python-float constant is rounded to float32 where it meets float32 data
-// (NEP 50), operations run in float32 in the source order, nothing is fused
-// (-ffp-contract=off).  |V| = (u**2 + v**2) ** 0.5 goes through the device
-// copy of glibc's powf (libm_powf.hpp), as NumPy's float32 scalar `**` does
-// in the reference, so the predictor is bit-exact too.
+// The one-thread-per-cell kernels and their launchers are the float
+// instantiations of fields2d_cells.hpp.  Arithmetic follows the reference as
+// it executes in NumPy-scalar form: every Python-float constant is rounded to
+// float32 where it meets float32 data (NEP 50), operations run in float32 in
+// the source order, nothing is fused (-ffp-contract=off).  |V| = (u**2 +
+// v**2) ** 0.5 goes through the device copy of glibc's powf (libm_powf.hpp),
+// as NumPy's float32 scalar `**` does in the reference, so the predictor is
+// bit-exact too.
 //
-// These kernels are one-pass per cell and HBM-bound; the fused predictor
-// reads u, v once (5-point neighbourhoods from L1/L2) and writes u*, v*, tau.
+// This file adds what only the float32 step has: clean_divergence_fast's phi
+// sweep on a skewed copy of phi and div, and the predictor's tuning entry
+// points.
 #include <atomic>
 #include <map>
 #include <mutex>
 
-#include "common.hpp"
-#include "internal.hpp"
-#include "libm_powf.hpp"
-#include "pred_rows.hpp"
+#include "fields2d_cells.hpp"
 
 namespace cfd {
 
-using PredConst = PredK<float>;
-static PredConst make_pred_const(double dx, double dy) { return make_pred_k<float>(dx, dy); }
-
-// compute_supg_stabilization_fast body, v5.py:155-161: vel_mag =
-// (u**2 + v**2) ** 0.5 on float32 scalars, i.e. libm powf three times
-// (powf_sq / powf_sqrt: glibc powf at y = 2 / 0.5 bit for bit, with a cheap
-// exact path away from rounding midpoints -- libm_powf.hpp)
-__device__ inline float supg_tau(float u, float v, float nu, float dt, const PredConst &k,
-                                 const libm::PowfTables &T = libm::kPowfTables) {
-    const float vm = libm::powf_sqrt(libm::powf_sq(u, T) + libm::powf_sq(v, T), T);
-    if (vm > k.eps) {
-        const float pe = (vm * k.h) / (nu + k.eps);
-        const float half = pe / 2.0f;
-        const float lim = half < 1.0f ? half : 1.0f;  // Python min(1.0, Pe/2.0)
-        return (k.h / (2.0f * vm)) * lim;
-    }
-    return dt / 2.0f;
-}
-__device__ inline bool interior(int i, int j, int ny, int nx) {
-    return i >= 1 && i < ny - 1 && j >= 1 && j < nx - 1;
-}
-
-#define CFD_2D_INDEX                                     \
-    const int j = blockIdx.x * blockDim.x + threadIdx.x; \
-    const int i = blockIdx.y;                            \
-    if (j >= nx) return;                                 \
-    const size_t c = (size_t)i * nx + j;
-
-__global__ void k_supg_tau(const float *__restrict__ u, const float *__restrict__ v,
-                           const float *__restrict__ nu_eff, float nu_s, float *__restrict__ tau,
-                           int ny, int nx, float dt, PredConst k) {
-    CFD_2D_INDEX
-    float t = 0.0f;  // np.zeros_like boundary ring
-    if (interior(i, j, ny, nx)) t = supg_tau(u[c], v[c], nu_eff ? nu_eff[c] : nu_s, dt, k);
-    tau[c] = t;
-}
-
-__global__ void k_conv_supg(const float *__restrict__ u, const float *__restrict__ v,
-                            const float *__restrict__ f, const float *__restrict__ tau,
-                            float *__restrict__ conv, int ny, int nx, PredConst k) {
-    CFD_2D_INDEX
-    float r = 0.0f;
-    if (interior(i, j, ny, nx))
-        r = conv_supg(u[c], v[c], f[c], f[c + 1], f[c - 1], f[c + nx], f[c - nx], tau[c], k);
-    conv[c] = r;
-}
-
-__global__ void k_conv_upwind(const float *__restrict__ u, const float *__restrict__ v,
-                              const float *__restrict__ f, float *__restrict__ conv, int ny, int nx,
-                              PredConst k) {
-    CFD_2D_INDEX
-    float r = 0.0f;
-    if (interior(i, j, ny, nx))
-        r = conv_upwind(u[c], v[c], f[c], f[c + 1], f[c - 1], f[c + nx], f[c - nx], k);
-    conv[c] = r;
-}
-
-__global__ void k_laplacian(const float *__restrict__ f, const float *__restrict__ nu_eff, float nu_s,
-                            float *__restrict__ lap, int ny, int nx, PredConst k) {
-    CFD_2D_INDEX
-    float r = 0.0f;
-    if (interior(i, j, ny, nx))
-        r = laplacian(nu_eff ? nu_eff[c] : nu_s, f[c], f[c + 1], f[c - 1], f[c + nx], f[c - nx], k);
-    lap[c] = r;
-}
-
-// compute_smagorinsky_viscosity_fast, v5.py:96-110 (smag_nut, pred_rows.hpp)
-__global__ void k_smagorinsky(const float *__restrict__ u, const float *__restrict__ v, float *__restrict__ nut,
-                              int ny, int nx, float cles, PredConst k) {
-    CFD_2D_INDEX
-    float r = 0.0f;
-    if (interior(i, j, ny, nx)) r = smag_nut(u[c], v[c], u[c + 1], v[c + 1], u[c + nx], v[c + nx], cles, k);
-    nut[c] = r;
-}
-
-// Fused predictor, v5.py:388-403: u* = u + dt*(-conv_u + lap_u), likewise v.
-// LES: nu_eff holds nu_t and nu_eff = (nu_s + nu_t) + art per cell (v5.py:388).
-template <bool SUPG, bool LES = false>
-__global__ __launch_bounds__(256) void k_predictor(const float *__restrict__ u,
-                                                   const float *__restrict__ v,
-                                                   const float *__restrict__ nu_eff, float nu_s,
-                                                   float *__restrict__ us, float *__restrict__ vs,
-                                                   float *__restrict__ tau_out, int ny, int nx,
-                                                   float dt, PredConst k, float art = 0.0f) {
-    CFD_2D_INDEX
-    const float uc = u[c], vc = v[c];
-    float cu = 0.0f, cv = 0.0f, lu = 0.0f, lv = 0.0f, t = 0.0f;
-    if (interior(i, j, ny, nx)) {
-        const float nu = LES ? (nu_s + nu_eff[c]) + art : (nu_eff ? nu_eff[c] : nu_s);
-        const float uE = u[c + 1], uW = u[c - 1], uN = u[c + nx], uS = u[c - nx];
-        const float vE = v[c + 1], vW = v[c - 1], vN = v[c + nx], vS = v[c - nx];
-        if (SUPG) {
-            t = supg_tau(uc, vc, nu, dt, k);
-            cu = conv_supg(uc, vc, uc, uE, uW, uN, uS, t, k);
-            cv = conv_supg(uc, vc, vc, vE, vW, vN, vS, t, k);
-        } else {
-            cu = conv_upwind(uc, vc, uc, uE, uW, uN, uS, k);
-            cv = conv_upwind(uc, vc, vc, vE, vW, vN, vS, k);
-        }
-        lu = laplacian(nu, uc, uE, uW, uN, uS, k);
-        lv = laplacian(nu, vc, vE, vW, vN, vS, k);
-    }
-    us[c] = uc + dt * (-cu + lu);
-    vs[c] = vc + dt * (-cv + lv);
-    if (tau_out) tau_out[c] = t;  // 0 without SUPG (v5.py:292: never assigned without SUPG)
-}
-
-// compute_divergence_fast, v5.py:178-187 (+ max|div| diagnostic, v5.py:410)
-__global__ __launch_bounds__(256) void k_divergence(const float *__restrict__ u,
-                                                    const float *__restrict__ v,
-                                                    float *__restrict__ div, int ny, int nx,
-                                                    float cx, float cy, float *absmax) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    float m = 0.0f;
-    if (j < nx) {
-        const size_t c = (size_t)i * nx + j;
-        float d = 0.0f;
-        if (interior(i, j, ny, nx)) d = (u[c + 1] - u[c - 1]) * cx + (v[c + nx] - v[c - nx]) * cy;
-        div[c] = d;
-        const float a = fabsf(d);
-        if (a > m) m = a;
-    }
-    if (absmax) wave_reduce_max_store(m, absmax);
-}
-
-// compute_gradient_fast, v5.py:189-200
-__global__ void k_gradient(const float *__restrict__ phi, float *__restrict__ gx,
-                           float *__restrict__ gy, int ny, int nx, float cx, float cy) {
-    CFD_2D_INDEX
-    float a = 0.0f, b = 0.0f;
-    if (interior(i, j, ny, nx)) {
-        a = (phi[c + 1] - phi[c - 1]) * cx;
-        b = (phi[c + nx] - phi[c - nx]) * cy;
-    }
-    gx[c] = a;
-    gy[c] = b;
-}
-
-// v5.py:413-417: gradient of phi, then u = u* - dt*dpdx, v = v* - dt*dpdy;
-// gradmax <- max sqrt(dpdx^2 + dpdy^2) (v5.py:414-415 diagnostic).
-__global__ __launch_bounds__(256) void k_project(const float *__restrict__ phi,
-                                                 const float *__restrict__ us,
-                                                 const float *__restrict__ vs,
-                                                 float *__restrict__ u, float *__restrict__ v,
-                                                 int ny, int nx, float cx, float cy, float dt,
-                                                 float *gradmax) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    float m = 0.0f;
-    if (j < nx) {
-        const size_t c = (size_t)i * nx + j;
-        float a = 0.0f, b = 0.0f;
-        if (interior(i, j, ny, nx)) {
-            a = (phi[c + 1] - phi[c - 1]) * cx;
-            b = (phi[c + nx] - phi[c - nx]) * cy;
-        }
-        u[c] = us[c] - dt * a;
-        v[c] = vs[c] - dt * b;
-        if (gradmax) {
-            const float g = sqrtf(a * a + b * b);
-            if (g > m) m = g;
-        }
-    }
-    if (gradmax) wave_reduce_max_store(m, gradmax);
-}
-
 // ------------------------------------------------------------ epilogue
-// clean_divergence_fast phi sweep (v5.py:250-253) in the serial lexicographic
-// order: a single workgroup walks the anti-diagonals; every cell of a
-// diagonal depends only on earlier diagonals (W, S: new) and later ones
-// (E, N: old), so updating one diagonal at a time reproduces the serial loop
-// exactly.  Thread t owns row b0+t of a band of blockDim rows and updates
-// column j = s - t + 1 at step s, so the NEW values never go through global
-// memory: W is the thread's own last output (a register), S the output of
-// thread t-1 one step earlier (LDS, double-buffered by step parity, one
-// barrier per step).  The OLD values -- E, div, and N -- are fetched PD steps
-// ahead (N within a wave is lane t+1's E of the same step, by DPP).  Row b0-1
-// (the previous band, finished) and the boundary rows are fetched like E.
-__global__ __launch_bounds__(1024) void k_lex_gs_sweep(float *__restrict__ phi,
-                                                       const float *__restrict__ div, int ny,
-                                                       int nx, float cx, float cy, float cd) {
-    constexpr int PD = 4;  // prefetch distance (steps)
-    __shared__ float outb[2][1024];
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63;
-    const int imax = ny - 2, jmax = nx - 2;
-    for (int b0 = 1; b0 <= imax; b0 += nt) {
-        __threadfence();  // the previous band's rows are final and visible
-        __syncthreads();
-        const int nrows = min(nt, imax - b0 + 1);
-        const int i = b0 + t;
-        const bool rowok = t < nrows;
-        const size_t rowc = (size_t)(rowok ? i : 0) * nx;
-        // N from memory for the last row of the band / grid and for lane 63
-        // (its lower neighbour row is in another wave); S for thread 0
-        const bool nmem = lane == 63 || t == nrows - 1;
-        float qE[PD], qD[PD], qN[PD], qS[PD];
-        auto fetch = [&](int st, float &e, float &d, float &n, float &sv) {
-            const int j = st - t + 1;
-            const bool act = rowok && j >= 1 && j <= jmax;
-            e = (rowok && j >= 0 && j <= jmax) ? phi[rowc + j + 1] : 0.f;
-            d = act ? div[rowc + j] : 0.f;
-            n = (act && nmem) ? phi[rowc + j + nx] : 0.f;
-            sv = (act && t == 0) ? phi[rowc + j - nx] : 0.f;
-        };
-#pragma unroll
-        for (int p = 0; p < PD; ++p) fetch(p, qE[p], qD[p], qN[p], qS[p]);
-        float w = rowok ? phi[rowc] : 0.f;  // phi(i, 0): W of column 1
-        const int nsteps = nrows - 1 + jmax;
-        for (int st = 0; st < nsteps; ++st) {
-            const int j = st - t + 1;
-            const bool act = rowok && j >= 1 && j <= jmax;
-            const float E = qE[0], D = qD[0], Nm = qN[0], S0 = qS[0];
-            const float nup = dpp_from_upper(E);  // lane t+1's E: old phi(i+1, j)
-#pragma unroll
-            for (int p = 0; p + 1 < PD; ++p) {
-                qE[p] = qE[p + 1];
-                qD[p] = qD[p + 1];
-                qN[p] = qN[p + 1];
-                qS[p] = qS[p + 1];
-            }
-            fetch(st + PD, qE[PD - 1], qD[PD - 1], qN[PD - 1], qS[PD - 1]);
-            if (act) {
-                const float S = t == 0 ? S0 : outb[(st + 1) & 1][t - 1];  // thread t-1 at step st-1
-                const float N = nmem ? Nm : nup;
-                const float a = cx * (E + w);
-                const float b = cy * (N + S);
-                const float v = ((a + b) - D) * cd;
-                phi[rowc + j] = v;
-                w = v;
-                outb[st & 1][t] = v;
-            }
-            __syncthreads();
-        }
-    }
-}
-
+// clean_divergence_fast's phi sweep (v5.py:250-253) in the serial
+// lexicographic order; k_lex_gs_sweep (fields2d_cells.hpp) says why walking
+// the anti-diagonals reproduces the serial loop exactly.
+//
 // The sweep on a SKEWED copy of phi and div (r05, the default): the r02-r04
 // staged kernels kept phi row-major, so the diagonal a wave touches per step
 // (lane l: row r0 + l, column d - l) is 64 cache lines, and a CU's vector
@@ -692,163 +461,6 @@ __global__ __launch_bounds__(64) void k_lex_gs_skew_mc(SkewArgs sa) {
     lex_skew_wave<true>(sa, (int)blockIdx.x, 0, 1, (int)threadIdx.x, nullptr, nullptr);
 }
 
-// u[1:-1,1:-1] -= grad_x[1:-1,1:-1] (no dt: v5.py:255-256)
-__global__ void k_sub_gradient(const float *__restrict__ phi, float *__restrict__ u,
-                               float *__restrict__ v, int ny, int nx, float cx, float cy) {
-    CFD_2D_INDEX
-    if (!interior(i, j, ny, nx)) return;
-    const float a = (phi[c + 1] - phi[c - 1]) * cx;
-    const float b = (phi[c + nx] - phi[c - nx]) * cy;
-    u[c] = u[c] - a;
-    v[c] = v[c] - b;
-}
-
-// apply_boundary_conditions, v5.py:349-360.  Net effect of the eight
-// assignments in order: rows 0 and ny-1 end at 0; other rows get the inlet
-// u = f32(V_inf*(1 + pert_scale*sin(2*pi*y/y_max + 0.02*step))), v = 0 at
-// x = 0 and a zero-gradient outlet copy from x = nx-2.
-__global__ void k_bc(float *__restrict__ u, float *__restrict__ v, const double *__restrict__ y,
-                     int ny, int nx, double y_max, double v_inf, int step) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nx) {  // top / bottom rows
-        u[t] = 0.0f;
-        v[t] = 0.0f;
-        u[(size_t)(ny - 1) * nx + t] = 0.0f;
-        v[(size_t)(ny - 1) * nx + t] = 0.0f;
-    }
-    const int i = t;
-    if (i >= 1 && i < ny - 1) {
-        const double s = (double)step;
-        double scale = s / 1000.0;
-        scale = (1.0 < scale ? 1.0 : scale) * 0.01;
-        const double two_pi = 2.0 * 3.141592653589793;
-        const double pert = scale * sin(two_pi * y[i] / y_max + 0.02 * s);
-        const size_t r = (size_t)i * nx;
-        u[r] = (float)(v_inf * (1.0 + pert));
-        v[r] = 0.0f;
-        u[r + nx - 1] = u[r + nx - 2];
-        v[r + nx - 1] = v[r + nx - 2];
-    }
-}
-
-// Lid-driven cavity walls (BASELINE config 1; the reference has no
-// incompressible cavity, so the walls follow the assignment pattern of
-// v5.py:349-360): no-slip u = v = 0 on the left, right and bottom walls, the
-// lid u = u_lid, v = 0 on the top row y = y_max (row ny-1), the lid written
-// last so it owns the two top corners.
-__global__ void k_lid_bc(float *__restrict__ u, float *__restrict__ v, int ny, int nx, float u_lid) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < ny - 1) {  // side walls, rows 0 .. ny-2
-        const size_t r = (size_t)t * nx;
-        u[r] = 0.0f;
-        v[r] = 0.0f;
-        u[r + nx - 1] = 0.0f;
-        v[r + nx - 1] = 0.0f;
-    }
-    if (t < nx) {
-        u[t] = 0.0f;  // bottom wall
-        v[t] = 0.0f;
-        u[(size_t)(ny - 1) * nx + t] = u_lid;  // lid
-        v[(size_t)(ny - 1) * nx + t] = 0.0f;
-    }
-}
-
-// apply_ibm_fast, v5.py:228-237 (float64 mask => float64 arithmetic)
-__global__ void k_ibm(float *__restrict__ u, float *__restrict__ v, const double *__restrict__ m,
-                      int n, double fs) {
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-        const double mv = m[c];
-        if (mv > 0.0) {
-            const double f = 1.0 - mv * fs;
-            u[c] = (float)((double)u[c] * f);
-            v[c] = (float)((double)v[c] * f);
-        }
-    }
-}
-
-__global__ void k_clip(float *__restrict__ a, size_t n, float lo, float hi) {
-    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < n;
-         c += (size_t)gridDim.x * blockDim.x) {
-        const float x = a[c];
-        a[c] = x < lo ? lo : (x > hi ? hi : x);  // NaN passes through like np.clip
-    }
-}
-
-// ------------------------------------------------------------ reductions
-__global__ void k_absmax(const float *__restrict__ a, const float *__restrict__ b, size_t n,
-                         float *out) {
-    float m = 0.0f;
-    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < n;
-         c += (size_t)gridDim.x * blockDim.x) {
-        float x = fabsf(a[c]);
-        if (x > m) m = x;
-        if (b) {
-            x = fabsf(b[c]);
-            if (x > m) m = x;
-        }
-    }
-    wave_reduce_max_store(m, out);
-}
-
-// mean of 0.5*(u^2 + v^2) (v5.py:362-363, :431-432); each cell's energy in
-// float32 like NumPy, the sum in float64.
-__global__ void k_energy_sum(const float *__restrict__ u, const float *__restrict__ v, size_t n,
-                             double *out) {
-    double s = 0.0;
-    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < n;
-         c += (size_t)gridDim.x * blockDim.x) {
-        const float e = 0.5f * (u[c] * u[c] + v[c] * v[c]);
-        s += (double)e;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-    if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
-}
-
-__global__ void k_scale_double(double *p, double f) { *p = *p * f; }
-
-// compute_vorticity + nanmax(|w|), v5.py:365-373, :427-428: masked cells are
-// NaN (skipped), the boundary ring is 0.
-__global__ void k_vort_absmax(const float *__restrict__ u, const float *__restrict__ v,
-                              const uint8_t *__restrict__ mask, int ny, int nx, float dx2,
-                              float dy2, float *out) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
-    float m = 0.0f;
-    if (j < nx) {
-        const size_t c = (size_t)i * nx + j;
-        if (interior(i, j, ny, nx) && !(mask && mask[c])) {
-            const float w = (v[c + 1] - v[c - 1]) / dx2 - (u[c + nx] - u[c - nx]) / dy2;
-            const float a = fabsf(w);
-            if (a > m) m = a;
-        }
-    }
-    wave_reduce_max_store(m, out);
-}
-
-// compute_vorticity, v5.py:365-373: interior central differences, boundary
-// ring 0, masked cells NaN.
-__global__ void k_vorticity(const float *__restrict__ u, const float *__restrict__ v,
-                            const uint8_t *__restrict__ mask, float *__restrict__ w, int ny,
-                            int nx, float dx2, float dy2) {
-    CFD_2D_INDEX
-    float r = 0.0f;
-    if (interior(i, j, ny, nx)) r = (v[c + 1] - v[c - 1]) / dx2 - (u[c + nx] - u[c - nx]) / dy2;
-    if (mask && mask[c]) r = __builtin_nanf("");
-    w[c] = r;
-}
-
-__global__ void k_nonfinite(const float *__restrict__ a, const float *__restrict__ b, size_t n,
-                            int *out) {
-    int cnt = 0;
-    for (size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x; c < n;
-         c += (size_t)gridDim.x * blockDim.x) {
-        cnt += !isfinite(a[c]);
-        if (b) cnt += !isfinite(b[c]);
-    }
-    if (cnt) atomicAdd(out, cnt);
-}
-
 // NumPy float32 scalar power (glibc powf, libm_powf.hpp) elementwise: the
 // parity hook for the device powf the SUPG tau uses -- at y = 2 and 0.5 the
 // exact-path forms it calls (powf_sq / powf_sqrt), else the restatement.
@@ -857,8 +469,6 @@ __global__ void k_numpy_powf(const float *__restrict__ x, float y, float *__rest
          c += (size_t)gridDim.x * blockDim.x)
         out[c] = y == 2.0f ? libm::powf_sq(x[c]) : (y == 0.5f ? libm::powf_sqrt(x[c]) : libm::powf(x[c], y));
 }
-
-static dim3 grid2d(int ny, int nx) { return dim3(ceil_div(nx, 256), ny); }
 
 static thread_local int g_last_pred[3] = {-1, 0, 0};
 void set_last_predictor(int path, int tau, int vec) {
@@ -880,156 +490,50 @@ int pred_rows_resident(const void *f) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, 256, 0) != hipSuccess || per < 1) per = 1;
     return cache[key] = per * cus;
 }
-static int grid1d(size_t n) {
-    long b = (long)((n + 255) / 256);
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 }  // namespace cfd
 
 using namespace cfd;
 
-#define CFD_SHAPE2D(ny, nx) CFD_REQUIRE((ny) >= 1 && (nx) >= 1, "bad 2-D shape (%d, %d)", ny, nx)
-
 extern "C" {
 
 int cfd_supg_tau2d_f32(const float *u, const float *v, const float *nu_eff, float nu_eff_scalar,
                        float *tau, int ny, int nx, double dx, double dy, float dt, void *stream) {
-    CFD_REQUIRE(u && v && tau, "supg_tau2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_supg_tau, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, nu_eff,
-                       nu_eff_scalar, tau, ny, nx, dt, make_pred_const(dx, dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return supg_tau2d<float>("supg_tau2d", u, v, nu_eff, nu_eff_scalar, tau, ny, nx, dx, dy, dt, stream);
 }
 
 int cfd_convection_supg2d_f32(const float *u, const float *v, const float *phi, const float *tau,
                               float *conv, int ny, int nx, double dx, double dy, void *stream) {
-    CFD_REQUIRE(u && v && phi && tau && conv, "convection_supg2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_conv_supg, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, phi, tau,
-                       conv, ny, nx, make_pred_const(dx, dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return convection_supg2d<float>("convection_supg2d", u, v, phi, tau, conv, ny, nx, dx, dy, stream);
 }
 
 int cfd_convection_upwind2d_f32(const float *u, const float *v, const float *phi, float *conv,
                                 int ny, int nx, double dx, double dy, void *stream) {
-    CFD_REQUIRE(u && v && phi && conv, "convection_upwind2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_conv_upwind, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, phi,
-                       conv, ny, nx, make_pred_const(dx, dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return convection_upwind2d<float>("convection_upwind2d", u, v, phi, conv, ny, nx, dx, dy, stream);
 }
 
 int cfd_laplacian2d_f32(const float *phi, const float *nu_eff, float nu_eff_scalar, float *lap,
                         int ny, int nx, double dx, double dy, void *stream) {
-    CFD_REQUIRE(phi && lap, "laplacian2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_laplacian, grid2d(ny, nx), dim3(256), 0, as_stream(stream), phi, nu_eff,
-                       nu_eff_scalar, lap, ny, nx, make_pred_const(dx, dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
-}
-
-// cfd_predictor2d_f32 (les == false) and cfd_predictor2d_les_f32 (nu_eff null,
-// nu_s the molecular nu; nu_t may be null on the row march)
-static int predictor2d_f32(const char *who, const float *u, const float *v, const float *nu_eff, float nu_s,
-                           float *u_star, float *v_star, float *tau, int ny, int nx, double dx, double dy, float dt,
-                           int use_supg, void *stream, bool les, float art, double cs, float *nu_t) {
-    CFD_REQUIRE(u && v && u_star && v_star, "%s: null pointer", who);
-    CFD_REQUIRE(u_star != u && v_star != v && u_star != v && v_star != u,
-                "%s: outputs must not alias inputs", who);
-    CFD_REQUIRE(!nu_t || (nu_t != u && nu_t != v && nu_t != u_star && nu_t != v_star && nu_t != tau),
-                "%s: nu_t must not alias another array", who);
-    CFD_SHAPE2D(ny, nx);
-    const PredConst k = make_pred_const(dx, dy);
-    const float cles = les ? (float)smag_const(cs, dx, dy) : 0.0f;
-    hipStream_t s = as_stream(stream);
-    // cells per lane of the row march: the preferred count (tuning; default
-    // 2), halved until nx and every array's alignment allow it (1 always does)
-    int vec = tuning().pred_vec ? tuning().pred_vec : 2;
-    auto fits = [&](int w) {
-        const uintptr_t m = (uintptr_t)(4 * w - 1);
-        auto al = [&](const void *p_) { return !p_ || ((uintptr_t)p_ & m) == 0; };
-        return nx % w == 0 && al(u) && al(v) && al(u_star) && al(v_star) && al(tau) && al(nu_eff) && al(nu_t);
-    };
-    while (vec > 1 && !fits(vec)) vec /= 2;
-    const bool rows_ok = (size_t)ny * nx * sizeof(float) < ((size_t)1 << 31);
-    const bool rows = tuning().pred_variant != 1 && rows_ok;
-    CFD_REQUIRE(!les || rows || nu_t, "%s: the one-thread-per-cell path needs nu_t (it stores it, then reads it)",
-                who);
-    const int tau_mode = use_supg ? tuning().pred_tau : kTauExact;
-    const int tk = timing_begin(s, kTimingPredictor);
-    if (rows) {
-        PredRowArgs<float> a;
-        a.u = u;
-        a.v = v;
-        a.nu = nu_eff;
-        a.us = u_star;
-        a.vs = v_star;
-        a.tau = tau;  // zeros without SUPG
-        a.nu_s = nu_s;
-        a.dt = dt;
-        a.ny = ny;
-        a.nx = nx;
-        a.k = k;
-        a.les = les;
-        a.nut = nu_t;
-        a.art = art;
-        a.cles = cles;
-        CFD_CHECK_HIP(pred_rows_launch<float>(a, use_supg != 0, tau_mode, vec, tuning().pred_rows, s));
-        set_last_predictor(1, tau_mode, vec);
-    } else if (les) {
-        // the stand-alone nu_t pass, then nu_eff per cell from the stored nu_t
-        hipLaunchKernelGGL(k_smagorinsky, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_t, ny, nx, cles, k);
-        if (use_supg)
-            hipLaunchKernelGGL((k_predictor<true, true>), grid2d(ny, nx), dim3(256), 0, s, u, v, (const float *)nu_t,
-                               nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
-        else
-            hipLaunchKernelGGL((k_predictor<false, true>), grid2d(ny, nx), dim3(256), 0, s, u, v, (const float *)nu_t,
-                               nu_s, u_star, v_star, tau, ny, nx, dt, k, art);
-        set_last_predictor(0, kTauExact, 1);
-    } else if (use_supg) {
-        hipLaunchKernelGGL(k_predictor<true>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s, u_star,
-                           v_star, tau, ny, nx, dt, k, 0.0f);
-        set_last_predictor(0, kTauExact, 1);
-    } else {
-        hipLaunchKernelGGL(k_predictor<false>, grid2d(ny, nx), dim3(256), 0, s, u, v, nu_eff, nu_s, u_star,
-                           v_star, tau, ny, nx, dt, k, 0.0f);
-        set_last_predictor(0, kTauExact, 1);
-    }
-    timing_end(tk, s, 1);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return laplacian2d<float>("laplacian2d", phi, nu_eff, nu_eff_scalar, lap, ny, nx, dx, dy, stream);
 }
 
 int cfd_predictor2d_f32(const float *u, const float *v, const float *nu_eff, float nu_eff_scalar,
                         float *u_star, float *v_star, float *tau, int ny, int nx, double dx,
                         double dy, float dt, int use_supg, void *stream) {
-    return predictor2d_f32("predictor2d", u, v, nu_eff, nu_eff_scalar, u_star, v_star, tau, ny, nx, dx, dy, dt,
-                           use_supg, stream, false, 0.0f, 0.0, nullptr);
+    return predictor2d<float>("predictor2d", u, v, nu_eff, nu_eff_scalar, u_star, v_star, tau, ny, nx, dx, dy, dt,
+                              use_supg, stream, false, 0.0f, 0.0, nullptr);
 }
 
 int cfd_predictor2d_les_f32(const float *u, const float *v, float nu, float art_visc, double cs, float *u_star,
                             float *v_star, float *tau, float *nu_t, int ny, int nx, double dx, double dy, float dt,
                             int use_supg, void *stream) {
-    return predictor2d_f32("predictor2d_les", u, v, nullptr, nu, u_star, v_star, tau, ny, nx, dx, dy, dt, use_supg,
-                           stream, true, art_visc, cs, nu_t);
+    return predictor2d<float>("predictor2d_les", u, v, nullptr, nu, u_star, v_star, tau, ny, nx, dx, dy, dt, use_supg,
+                              stream, true, art_visc, cs, nu_t);
 }
 
 int cfd_smagorinsky2d_f32(const float *u, const float *v, float *nu_t, int ny, int nx, double dx, double dy,
                           double cs, void *stream) {
-    CFD_REQUIRE(u && v && nu_t, "smagorinsky2d: null pointer");
-    CFD_REQUIRE(nu_t != u && nu_t != v, "smagorinsky2d: nu_t must not alias an input");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_smagorinsky, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, nu_t, ny, nx,
-                       (float)smag_const(cs, dx, dy), make_pred_const(dx, dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return smagorinsky2d<float>("smagorinsky2d", u, v, nu_t, ny, nx, dx, dy, cs, stream);
 }
 
 // 0: auto (row march when the shape allows it), 1: one thread per cell
@@ -1061,33 +565,18 @@ int cfd_set_predictor2d_config(int variant, int rows, int cells_per_lane) {
 
 int cfd_divergence2d_f32(const float *u, const float *v, float *div, int ny, int nx, double dx,
                          double dy, float *absmax, void *stream) {
-    CFD_REQUIRE(u && v && div, "divergence2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_divergence, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, div, ny,
-                       nx, (float)(0.5 / dx), (float)(0.5 / dy), absmax);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return divergence2d<float>("divergence2d", u, v, div, ny, nx, dx, dy, absmax, stream);
 }
 
 int cfd_gradient2d_f32(const float *phi, float *grad_x, float *grad_y, int ny, int nx, double dx,
                        double dy, void *stream) {
-    CFD_REQUIRE(phi && grad_x && grad_y, "gradient2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_gradient, grid2d(ny, nx), dim3(256), 0, as_stream(stream), phi, grad_x,
-                       grad_y, ny, nx, (float)(0.5 / dx), (float)(0.5 / dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return gradient2d<float>("gradient2d", phi, grad_x, grad_y, ny, nx, dx, dy, stream);
 }
 
 int cfd_project2d_f32(const float *phi, const float *u_star, const float *v_star, float *u,
                       float *v, int ny, int nx, double dx, double dy, float dt, float *gradmax,
                       void *stream) {
-    CFD_REQUIRE(phi && u_star && v_star && u && v, "project2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_project, grid2d(ny, nx), dim3(256), 0, as_stream(stream), phi, u_star,
-                       v_star, u, v, ny, nx, (float)(0.5 / dx), (float)(0.5 / dy), dt, gradmax);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return project2d<float>("project2d", phi, u_star, v_star, u, v, ny, nx, dx, dy, dt, gradmax, stream);
 }
 
 size_t cfd_clean_divergence_workspace_bytes(int ny, int nx) {
@@ -1104,9 +593,6 @@ int cfd_clean_divergence2d_f32(float *u, float *v, int ny, int nx, double dx, do
     CFD_REQUIRE(u && v && ws, "clean_divergence2d: null pointer");
     CFD_SHAPE2D(ny, nx);
     hipStream_t s = as_stream(stream);
-    const size_t n = (size_t)ny * nx;
-    float *phi = reinterpret_cast<float *>(ws);
-    float *div = phi + n;
     const double dx2_inv = 1.0 / (dx * dx), dy2_inv = 1.0 / (dy * dy);
     const double denom_inv = 1.0 / (2.0 * (dx2_inv + dy2_inv));
     const float cx = (float)(0.5 / dx), cy = (float)(0.5 / dy);
@@ -1205,156 +691,64 @@ int cfd_clean_divergence2d_f32(float *u, float *v, int ny, int nx, double dx, do
         CFD_LAUNCH_CHECK();
         return CFD_OK;
     }
-    CFD_CHECK_HIP(hipMemsetAsync(phi, 0, n * sizeof(float), s));  // np.zeros_like (v5.py:242)
-    for (int it = 0; it < iterations; ++it) {
-        hipLaunchKernelGGL(k_divergence, grid2d(ny, nx), dim3(256), 0, s, u, v, div, ny, nx, cx, cy,
-                           (float *)nullptr);
-        if (ny > 2 && nx > 2)  // past the skewed layout's 2^31-byte offsets: the plain wavefront
-            hipLaunchKernelGGL(k_lex_gs_sweep, dim3(1), dim3(ny - 2 >= 1024 ? 1024 : 64 * ceil_div(ny - 2, 64)), 0, s,
-                               phi, div, ny, nx, (float)dx2_inv, (float)dy2_inv, (float)denom_inv);
-        hipLaunchKernelGGL(k_sub_gradient, grid2d(ny, nx), dim3(256), 0, s, phi, u, v, ny, nx, cx,
-                           cy);
-        CFD_LAUNCH_CHECK();
-    }
-    return CFD_OK;
+    // past the skewed layout's 2^31-byte offsets: the plain wavefront
+    return clean_divergence_plain<float>(u, v, ny, nx, dx, dy, iterations, ws, s);
 }
 
 int cfd_apply_bc2d_f32(float *u, float *v, const double *y, int ny, int nx, double y_max,
                        double v_inf, int step, void *stream) {
-    CFD_REQUIRE(u && v && y, "apply_bc2d: null pointer");
-    CFD_REQUIRE(ny >= 2 && nx >= 2, "apply_bc2d: grid must be at least 2x2");
-    const int n = ny > nx ? ny : nx;
-    hipLaunchKernelGGL(k_bc, dim3(ceil_div(n, 256)), dim3(256), 0, as_stream(stream), u, v, y, ny,
-                       nx, y_max, v_inf, step);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return apply_bc2d<float>("apply_bc2d", u, v, y, ny, nx, y_max, v_inf, step, stream);
 }
 
 int cfd_apply_lid_bc2d_f32(float *u, float *v, int ny, int nx, float u_lid, void *stream) {
-    CFD_REQUIRE(u && v, "apply_lid_bc2d: null pointer");
-    CFD_REQUIRE(ny >= 2 && nx >= 2, "apply_lid_bc2d: grid must be at least 2x2");
-    const int n = ny > nx ? ny : nx;
-    hipLaunchKernelGGL(k_lid_bc, dim3(ceil_div(n, 256)), dim3(256), 0, as_stream(stream), u, v, ny, nx, u_lid);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return apply_lid_bc2d<float>("apply_lid_bc2d", u, v, ny, nx, u_lid, stream);
 }
 
 int cfd_apply_ibm2d_f32(float *u, float *v, const double *ibm_mask, int n, double force_strength,
                         void *stream) {
-    CFD_REQUIRE(u && v && ibm_mask && n >= 0, "apply_ibm2d: bad arguments");
-    if (n == 0) return CFD_OK;
-    hipLaunchKernelGGL(k_ibm, dim3(grid1d(n)), dim3(256), 0, as_stream(stream), u, v, ibm_mask, n,
-                       force_strength);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return apply_ibm2d<float>("apply_ibm2d", u, v, ibm_mask, n, force_strength, stream);
 }
 
 int cfd_clip_f32(float *a, size_t n, float lo, float hi, void *stream) {
-    CFD_REQUIRE(a, "clip: null pointer");
-    if (n == 0) return CFD_OK;
-    hipLaunchKernelGGL(k_clip, dim3(grid1d(n)), dim3(256), 0, as_stream(stream), a, n, lo, hi);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return clip_field<float>("clip", a, n, lo, hi, stream);
 }
 
 int cfd_absmax_f32(const float *a, size_t n, float *out, void *stream) {
-    CFD_REQUIRE(a && out, "absmax: null pointer");
-    if (n == 0) return CFD_OK;
-    hipLaunchKernelGGL(k_absmax, dim3(grid1d(n)), dim3(256), 0, as_stream(stream), a,
-                       (const float *)nullptr, n, out);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return absmax2<float>("absmax", a, nullptr, n, out, stream);
 }
 
 int cfd_absmax2_f32(const float *a, const float *b, size_t n, float *out, void *stream) {
-    CFD_REQUIRE(a && b && out, "absmax2: null pointer");
-    if (n == 0) return CFD_OK;
-    hipLaunchKernelGGL(k_absmax, dim3(grid1d(n)), dim3(256), 0, as_stream(stream), a, b, n, out);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    CFD_REQUIRE(b, "absmax2: null pointer");
+    return absmax2<float>("absmax2", a, b, n, out, stream);
 }
 
 int cfd_energy_mean2d_f32(const float *u, const float *v, size_t n, double *out, void *stream) {
-    CFD_REQUIRE(u && v && out && n > 0, "energy_mean2d: bad arguments");
-    hipStream_t s = as_stream(stream);
-    if (n <= kEnergyOneBlock) {
-        if (unsigned *ws = energy_scratch(s))
-            hipLaunchKernelGGL((k_energy_mean_mb<float, false>), dim3(kEnergyBlocks), dim3(256), 0, s,
-                               const_cast<float *>(u), const_cast<float *>(v), n, out, float(0), float(0), ws);
-        else
-            hipLaunchKernelGGL((k_energy_mean_1blk<float, false>), dim3(1), dim3(1024), 0, s, const_cast<float *>(u),
-                               const_cast<float *>(v), n, out, float(0), float(0));
-        CFD_LAUNCH_CHECK();
-        return CFD_OK;
-    }
-    CFD_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(double), s));
-    hipLaunchKernelGGL(k_energy_sum, dim3(grid1d(n)), dim3(256), 0, s, u, v, n, out);
-    hipLaunchKernelGGL(k_scale_double, dim3(1), dim3(1), 0, s, out, 1.0 / (double)n);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return energy_mean2d<float, false>("energy_mean2d", const_cast<float *>(u), const_cast<float *>(v), n, out, 0.0f,
+                                       0.0f, stream);
 }
 
 int cfd_mean_f32(const float *a, size_t n, double *out, void *stream) {
-    CFD_REQUIRE(a && out && n > 0, "mean_f32: bad arguments");
-    hipStream_t s = as_stream(stream);
-    unsigned *ws = energy_scratch(s);
-    CFD_REQUIRE(ws, "mean_f32: no scratch for the partial sums");
-    hipLaunchKernelGGL(k_mean_mb<float>, dim3(kEnergyBlocks), dim3(256), 0, s, a, n, out, ws);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return mean_field<float>("mean_f32", a, n, out, stream);
 }
 
 int cfd_energy_mean_clip2d_f32(float *u, float *v, size_t n, double *out, float lo, float hi, void *stream) {
-    CFD_REQUIRE(u && v && out && n > 0, "energy_mean_clip2d_f32: bad arguments");
-    hipStream_t s = as_stream(stream);
-    if (n <= kEnergyOneBlock) {
-        if (unsigned *ws = energy_scratch(s))
-            hipLaunchKernelGGL((k_energy_mean_mb<float, true>), dim3(kEnergyBlocks), dim3(256), 0, s, u, v, n, out,
-                               lo, hi, ws);
-        else
-            hipLaunchKernelGGL((k_energy_mean_1blk<float, true>), dim3(1), dim3(1024), 0, s, u, v, n, out, lo, hi);
-        CFD_LAUNCH_CHECK();
-        return CFD_OK;
-    }
-    int rc = cfd_energy_mean2d_f32(u, v, n, out, stream);
-    if (!rc) rc = cfd_clip_f32(u, n, lo, hi, stream);
-    if (!rc) rc = cfd_clip_f32(v, n, lo, hi, stream);
-    return rc;
+    return energy_mean2d<float, true>("energy_mean_clip2d_f32", u, v, n, out, lo, hi, stream);
 }
 
 int cfd_apply_bc_ibm2d_f32(float *u, float *v, const double *y, int ny, int nx, double y_max, double v_inf, int step,
                            const double *ibm_mask, double force_strength, void *stream) {
-    CFD_REQUIRE(u && v && y, "apply_bc_ibm2d_f32: null pointer");
-    CFD_REQUIRE(ny >= 2 && nx >= 2, "apply_bc_ibm2d_f32: grid must be at least 2x2");
-    int blocks = ceil_div(ny > nx ? ny : nx, 256);
-    if (ibm_mask) {
-        const int g = grid1d((size_t)ny * nx);
-        if (g > blocks) blocks = g;
-    }
-    hipLaunchKernelGGL(k_bc_ibm<float>, dim3(blocks), dim3(256), 0, as_stream(stream), u, v, y, ibm_mask, ny, nx,
-                       y_max, v_inf, step, force_strength);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return apply_bc_ibm2d<float>("apply_bc_ibm2d_f32", u, v, y, ny, nx, y_max, v_inf, step, ibm_mask, force_strength,
+                                 stream);
 }
 
 int cfd_vorticity_absmax2d_f32(const float *u, const float *v, const uint8_t *mask, int ny, int nx,
                                double dx, double dy, float *out, void *stream) {
-    CFD_REQUIRE(u && v && out, "vorticity_absmax2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_vort_absmax, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, mask,
-                       ny, nx, (float)(2.0 * dx), (float)(2.0 * dy), out);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return vorticity2d<float>("vorticity_absmax2d", u, v, mask, nullptr, out, ny, nx, dx, dy, stream);
 }
 
 int cfd_vorticity2d_f32(const float *u, const float *v, const uint8_t *mask, float *w, int ny,
                         int nx, double dx, double dy, void *stream) {
-    CFD_REQUIRE(u && v && w, "vorticity2d: null pointer");
-    CFD_SHAPE2D(ny, nx);
-    hipLaunchKernelGGL(k_vorticity, grid2d(ny, nx), dim3(256), 0, as_stream(stream), u, v, mask, w,
-                       ny, nx, (float)(2.0 * dx), (float)(2.0 * dy));
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return vorticity2d<float>("vorticity2d", u, v, mask, w, nullptr, ny, nx, dx, dy, stream);
 }
 
 int cfd_numpy_powf_f32(const float *x, float y, float *out, size_t n, void *stream) {
@@ -1366,13 +760,7 @@ int cfd_numpy_powf_f32(const float *x, float y, float *out, size_t n, void *stre
 }
 
 int cfd_nonfinite_count_f32(const float *a, const float *b, size_t n, int *out, void *stream) {
-    CFD_REQUIRE(a && out, "nonfinite_count: null pointer");
-    hipStream_t s = as_stream(stream);
-    CFD_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(int), s));
-    if (n == 0) return CFD_OK;
-    hipLaunchKernelGGL(k_nonfinite, dim3(grid1d(n)), dim3(256), 0, s, a, b, n, out);
-    CFD_LAUNCH_CHECK();
-    return CFD_OK;
+    return nonfinite_count<float>("nonfinite_count", a, b, n, out, stream);
 }
 
 }  // extern "C"
