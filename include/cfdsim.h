@@ -491,7 +491,9 @@ int cfd_predictor3d_les_zper_f32(const float *u, const float *v, const float *w,
  * temperature -- float32 operations in this order, nothing fused; the face
  * cells keep f; tau and nu_t are the plain predictor's.  b = (0, 0, 0) or
  * T == t_ref everywhere gives the plain predictor's values (a -0.0 may become
- * +0.0).  T is an input of the fields' shape: NULL is refused, and it must not
+ * +0.0) where T and t_ref are finite: there is no shortcut for a zero
+ * component, so a non-finite T makes NaN through 0 * Inf (b_f = 0) or
+ * Inf - Inf (T == t_ref == +-Inf), and a NaN T makes NaN.  T is an input of the fields' shape: NULL is refused, and it must not
  * alias an output.  The term is part of both predictor kernels (one more
  * 4-byte read per cell: the plane march keeps its own rows of T one plane
  * ahead, no halo), so cfd_set_predictor3d_config and

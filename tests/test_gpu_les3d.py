@@ -20,6 +20,7 @@ from cfd_simulations_amd._lib import call, ptr, stream_handle
 from cfd_simulations_amd.solver import LesCavity3DConfig, LidDrivenCavity3DConfig, LidDrivenCavity3DSolver
 from les3d_reference import (Cavity3DLesReference, nu_eff3d_numpy, predictor3d_les_numpy, predictor3d_nu_numpy,
                              smag3d_q_numpy, smagorinsky3d_numpy)
+from poisson_edge_reference import describe_difference, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -100,8 +101,13 @@ def last_path():
     return _lib.lib().cfd_get_last_predictor3d_path(ctypes.byref(cpl)), cpl.value
 
 
-def eq(got, want, what, equal_nan=False):
-    assert np.array_equal(host(got), want, equal_nan=equal_nan), what
+def eq(got, want, what, bits=False):
+    """np.array_equal; bits: same_bits (NaNs at the same cells, -0.0 apart
+    from +0.0), for references that hold NaN."""
+    if bits:
+        assert same_bits(host(got), want), (what, describe_difference(host(got), want))
+    else:
+        assert np.array_equal(host(got), want), what
 
 
 def check_nu(shape, supg, label=""):
@@ -271,15 +277,15 @@ def test_nonfinite_and_huge_inputs(supg):
         call("cfd_set_predictor3d_config", *cfg)
         got = K.predictor3d_fused_les(du, dv, dw, *SPT, DT, NU, ART, CS, supg)
         for name, t in zip(OUT, got):
-            eq(t, ref[name], (name, cfg), equal_nan=True)
-    eq(K.compute_smagorinsky_viscosity3d(du, dv, dw, *SPT, CS), ref["nu_t"], "nu_t", equal_nan=True)
+            eq(t, ref[name], (name, cfg), bits=True)
+    eq(K.compute_smagorinsky_viscosity3d(du, dv, dw, *SPT, CS), ref["nu_t"], "nu_t", bits=True)
     ne = nu_eff3d_numpy(ref["nu_t"], NU, ART)
     refn = predictor3d_nu_numpy(u, v, w, ne, dt=DT, use_supg=supg, **SP)
     for cfg in ((1, 0, 0), (2, 2, 4)):
         call("cfd_set_predictor3d_config", *cfg)
         got = K.predictor3d_fused(du, dv, dw, *SPT, DT, dev(ne), supg)
         for name, t in zip(OUT[:4], got):
-            eq(t, refn[name], (name, cfg, "array"), equal_nan=True)
+            eq(t, refn[name], (name, cfg, "array"), bits=True)
 
 
 def test_les_counts_on_the_predictor_timing_channel():
