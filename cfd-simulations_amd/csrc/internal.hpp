@@ -143,6 +143,22 @@ int jacobi3d_blocked_pass(int k, const float *in, float *out, const float *src, 
                           int nx, int zb, int ze, int fixed_lo, int fixed_hi, float h2, float dt,
                           bool pre, hipStream_t s);
 int jacobi3d_tb_prefetch();  // planes of prefetch in the blocked kernel (1 or 2)
+// The passes of a Jacobi solve of `iters` sweeps: a first pass of k1 sweeps,
+// then passes of K, any remainder last.  first: the first pass is the fused
+// one (jacobi3d_tbr_first_pass), its k1 = 2..4 chosen so that the passes of K
+// that follow need no shorter remainder pass where that can be had (k1 =
+// iters mod K when that is 2 or 3, K when it is 0); else k1 = min(K, iters).
+struct JacobiSchedule {
+    int iters, K, k1, npass;
+    bool first;
+    // sweeps of the pass that follows `done` sweeps
+    int depth(int done) const { return done == 0 ? k1 : iters - done < K ? iters - done : K; }
+    // Whether the first pass writes phi (else phi_tmp).  From a zero start
+    // nothing of phi is read, so the first pass writes the buffer that makes
+    // the last pass land in phi; from a guess it reads phi and writes phi_tmp.
+    bool first_into_phi(bool zero) const { return zero && npass % 2 == 1; }
+};
+JacobiSchedule jacobi3d_schedule(int iters, int K, bool first_ok);
 // jacobi3d_tbr.hip: K = 2..4 sweeps per pass with several rows per wave (tall tiles)
 // CUs the tall-tile launches may plan for on this host thread: all of them,
 // minus those a slab solve reserved for its exchange stream (set_cu_reserve).
@@ -155,8 +171,8 @@ int jacobi3d_tbr_pass(int K, int rows, const float *in, float *out, const float 
 int jacobi3d_tbr_first_pass(int K, float *out, const float *div, float *rhs_out, const float *in,
                             int nz, int ny, int nx, int zb, int ze, int fixed_lo, int fixed_hi,
                             float h2, float dt, int zchunk, bool zero, hipStream_t s);
-// jacobi2d_tbk.hip: one temporally blocked 2-D pass of K sweeps (T, VEC =
-// float, 4 / double, 2)
+// jacobi2d_tbk.hpp (instantiated in jacobi2d_tbk_f32.hip / _f64.hip): one
+// temporally blocked 2-D pass of K sweeps (T, VEC = float, 4 / double, 2)
 template <typename T, int VEC>
 int jacobi2d_tbk_pass(int K, const T *in, T *out, const T *div, const uint8_t *mask, int ny, int nx,
                       T dx2, T dtv, bool pre, hipStream_t s);
@@ -208,9 +224,17 @@ inline size_t rbgs_base_bytes(int iterations) {
     return 16 + sizeof(float) * (size_t)(1 + kGsSlotRows) * (size_t)(iterations > 0 ? iterations : 1);
 }
 
-// 3-D red-black GS (poisson3d.hip / jacobi3d_tb.hip)
+// 3-D red-black GS (poisson3d.hip / jacobi3d_tbr.hip)
 struct RbgsConsts {
     float cx, cy, cz, cd, dt_inv, tol;
+};
+// The planes a GS solve updates, [zb, ze) of a local array of nz planes whose
+// plane 0 is global plane zoff.  fixed_lo / fixed_hi: the plane next to that
+// end is a Dirichlet plane (else a ghost, whose intermediate colours the
+// fused passes recompute).  ghost: the depth of the periodic ghost planes on
+// either side of the range, wrapped after every pass; 0 = not periodic.
+struct RbgsRange {
+    int nz, zb, ze, fixed_lo, fixed_hi, zoff, ghost;
 };
 RbgsConsts rbgs3d_consts(double dx, double dy, double dz, float dt, double tolerance);
 // whether the fused out-of-place pass applies (no mask, float4 layout, blocking on)
@@ -221,12 +245,17 @@ bool rbgs3d_fused_ok(const float *phi, const float *phi_tmp, const float *div, c
 int rbgs3d_colour_pass(int colour, float *phi, const float *div, const uint8_t *mask, int ny,
                        int nx, int z0, int z1, int zoff, const RbgsConsts &k, RbgsWs *ws, int it,
                        hipStream_t s, bool mask2d = false);
-int rbgs3d_iters_per_pass();  // slab solves: 1, or 2 (blocking depth 4)
+int rbgs3d_iters_per_pass();  // slab solves: 1, or 2 (blocking depth 4 or auto)
 int rbgs3d_half_per_pass();   // single-GPU solves: half-sweeps per pass, 2..4 (auto 4)
-int rbgs3d_fused_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
-                      int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int it,
-                      int iters, RbgsWs *ws, hipStream_t s, int lag = 0);
 int rbgs3d_half_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
                      int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int h0,
                      int levels, RbgsWs *ws, hipStream_t s, int lag, const uint8_t *mask2d = nullptr);
+// The end of a fused solve of H half-sweeps in passes of P (2..4) over range
+// r: the count of iterations done; a stop inside a pass rolled back by
+// re-running that pass's half-sweeps up to the stop, one launch per possible
+// count (2c - P j is even when P is; none when tolerance <= 0, which cannot
+// stop); phi <- the buffer that holds the result.
+int rbgs3d_resolve_stop(float *phi, float *phi_tmp, const float *div, const RbgsRange &r, int ny, int nx,
+                        const RbgsConsts &k, int P, int H, RbgsWs *ws, int *iters_done,
+                        const uint8_t *mask2d, hipStream_t s);
 }  // namespace cfd

@@ -398,8 +398,9 @@ int launch_rhs_f32(const float *div, float *rhs, size_t n, float h2, float dt, h
 // ----------------------------------------------------------- red-black GS 3-D
 // In-place colour pass over planes [z0, z0 + gridDim.z) of a local array whose
 // plane 0 is global plane zoff (colour parity is global, so a slab's cells get
-// the colours they have in the whole grid).  The fused out-of-place pass is
-// jacobi3d_tb2<.., MODE_RBGS, ..> (jacobi3d_tb.hip); this one serves masks.
+// the colours they have in the whole grid).  The fused out-of-place passes
+// are the tall-tile kernel's (rbgs3d_tbr_pass, jacobi3d_tbr.hip); this one
+// serves 3-D masks and layouts the fused passes do not take.
 template <int C>
 __global__ __launch_bounds__(256) void rbgs3d_color(float *__restrict__ phi,
                                                     const float *__restrict__ div,
@@ -466,27 +467,16 @@ RbgsConsts rbgs3d_consts(double dx, double dy, double dz, float dt, double toler
     return k;
 }
 
-// Red-black GS iterations per fused pass of a slab solve: 2 when the blocking
-// depth is set to 4 levels (then a stop inside a pair is rolled back after the
-// loop), else 1.
-// Slab GS iterations per fused pass where the ghosts allow two (ghost 4):
-// 2 unless the blocking depth is set to 2 or 3 (or off).
+// Red-black GS iterations per fused pass of a slab solve where the ghosts
+// allow two (ghost 4): 2 when the blocking depth is 4 levels or auto (a stop
+// inside a pair is then rolled back after the loop), 1 when it is set to 2 or
+// 3 (or off).
 int rbgs3d_iters_per_pass() { return tuning().tb_steps == 4 || tuning().tb_steps == 0 ? 2 : 1; }
 // Half-sweeps (colour levels) per fused pass of a single-GPU solve: the
 // blocking depth, 2..4; auto = 4 (two iterations per HBM pass on the K = 4
 // tall tiles: 2.86 ms per pass at 1024^3 = 745 Gcell/s, against 2.19 ms per
 // 1.5 iterations = 730 at 3 levels, same box; r02).
 int rbgs3d_half_per_pass() { return tuning().tb_steps >= 2 ? tuning().tb_steps : 4; }
-
-// One fused GS pass of `iters` (1, 2) iterations: the tuned 2-level kernel
-// when its rows are set explicitly (5, 13), the tall-tile kernel otherwise
-// (always for a lagged stop test, which only the tall-tile kernel has).
-int rbgs3d_fused_pass(const float *in, float *out, const float *div, int nz, int ny, int nx, int zb,
-                      int ze, int fixed_lo, int fixed_hi, int zoff, const RbgsConsts &k, int it,
-                      int iters, RbgsWs *ws, hipStream_t s, int lag) {
-    return rbgs3d_half_pass(in, out, div, nz, ny, nx, zb, ze, fixed_lo, fixed_hi, zoff, k, 2 * it,
-                            2 * iters, ws, s, lag);
-}
 
 // The tile rows set for a GS pass of `levels` half-sweeps (2: 16, 18, 20, 28;
 // 3: 16, 18; 4: 15, 16), else 0 = auto.
@@ -506,6 +496,19 @@ int rbgs3d_half_pass(const float *in, float *out, const float *div, int nz, int 
                      int levels, RbgsWs *ws, hipStream_t s, int lag, const uint8_t *mask2d) {
     return rbgs3d_tbr_pass(in, out, div, nz, ny, nx, zb, ze, fixed_lo, fixed_hi, zoff, k, h0, levels,
                            ws, 0, 0, rbgs3d_half_rows(levels), s, lag, mask2d);
+}
+
+int rbgs3d_resolve_stop(float *phi, float *phi_tmp, const float *div, const RbgsRange &r, int ny, int nx,
+                        const RbgsConsts &k, int P, int H, RbgsWs *ws, int *iters_done,
+                        const uint8_t *mask2d, hipStream_t s) {
+    int rc;
+    if ((rc = launch_rbgs_count(ws, iters_done, s))) return rc;
+    for (int need = 1; need < P && k.tol > 0.f; ++need)
+        if (!(P % 2 == 0 && need % 2 == 1) &&
+            (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, r.nz, ny, nx, r.zb, r.ze, r.fixed_lo, r.fixed_hi, r.zoff, k,
+                                  0, need, ws, P, H, 0, s, 0, mask2d)))
+            return rc;
+    return launch_rbgs_copy(ws, phi, phi_tmp, (size_t)r.nz * ny * nx, P, s);
 }
 
 // One pass of k Jacobi sweeps over planes [zb, ze) (k = 1..4): the single
@@ -531,9 +534,16 @@ static bool jacobi3d_first_ok(const float *rhs_ws, bool vec_ok, int nz, int ny, 
            ny >= 3 && iters >= 2 && aligned16(rhs_ws);
 }
 
-// The blocked solve with a fused first pass of k1 = 2..4 sweeps (k1 =
-// iters mod K when that is 2 or 3, K when it is 0, so the passes of K that
-// follow need no shorter remainder pass), then passes of K, any remainder last.  zero: phi
+// The pass schedule of `iters` sweeps in passes of at most K (JacobiSchedule,
+// internal.hpp); first_ok: the first pass is the fused one.
+JacobiSchedule jacobi3d_schedule(int iters, int K, bool first_ok) {
+    const int r = iters % K;
+    int k1 = !first_ok ? K : (r == 2 || r == 3) ? r : r == 0 ? K : (K < 3 ? K : 3);
+    if (k1 > iters) k1 = iters;
+    return {iters, K, k1, iters > 0 ? 1 + (iters - k1 + K - 1) / K : 0, first_ok};
+}
+
+// The blocked solve with a fused first pass (jacobi3d_schedule).  zero: phi
 // starts as zeros (its boundary ring zeroed here in both arrays; nothing of
 // phi is read), and the first pass writes the array that makes the last
 // pass land in phi -- no zero fill, no RHS prologue, no final copy.  Else phi
@@ -542,25 +552,20 @@ static int jacobi3d_blocked_solve(const float *div, float *phi, float *phi_tmp, 
                                   int nz, int ny, int nx, float h2, float dt, int iters, bool zero,
                                   hipStream_t s) {
     int rc;
-    const int K = jacobi3d_tb_levels();
-    const int r = iters % K;
-    int k1 = (r == 2 || r == 3) ? r : r == 0 ? K : (K < 3 ? K : 3);
-    if (k1 > iters) k1 = iters;
-    const int rest = iters - k1;
-    const int npass = 1 + (rest + K - 1) / K;
-    float *first_out = zero && npass % 2 == 1 ? phi : phi_tmp;
+    const JacobiSchedule sch = jacobi3d_schedule(iters, jacobi3d_tb_levels(), true);
+    float *first_out = sch.first_into_phi(zero) ? phi : phi_tmp;
     if (zero) {
         if ((rc = launch_zero_faces3d(phi, phi_tmp, nz, ny, nx, s))) return rc;
     } else if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, nz, 0, nz - 1, s))) {
         return rc;
     }
     const int tk = timing_begin(s);
-    if ((rc = jacobi3d_tbr_first_pass(k1, first_out, div, rhs_ws, phi, nz, ny, nx, 1, nz - 1, 1, 1, h2,
+    if ((rc = jacobi3d_tbr_first_pass(sch.k1, first_out, div, rhs_ws, phi, nz, ny, nx, 1, nz - 1, 1, 1, h2,
                                       dt, tuning().tb_zchunk, zero, s)))
         return rc;
     float *a = first_out, *b = first_out == phi ? phi_tmp : phi;
-    for (int done = k1; done < iters;) {
-        const int k = iters - done < K ? iters - done : K;
+    for (int done = sch.k1; done < iters;) {
+        const int k = sch.depth(done);
         if ((rc = jacobi3d_blocked_pass(k, a, b, rhs_ws, nz, ny, nx, 1, nz - 1, 1, 1, h2, dt, true, s)))
             return rc;
         done += k;
@@ -688,35 +693,29 @@ int cfd_jacobi3d_f32(const float *div, float *phi, float *phi_tmp, float *rhs_ws
     float *a = phi, *b = phi_tmp;
     const int tk = timing_begin(s);
     const bool vec_ok = nx % 4 == 0 && aligned16(phi) && aligned16(phi_tmp) && aligned16(src);
-    if (jacobi3d_tb_enabled() && !mask && resid_every <= 0 && vec_ok && nz >= 3 && ny >= 3 &&
-        iters >= 2) {
-        // temporally blocked: passes of K sweeps, the remainder last
-        const int K = jacobi3d_tb_levels();
-        int done = 0;
-        while (done < iters) {
-            const int k = iters - done < K ? iters - done : K;
+    // temporally blocked (passes of K sweeps, the remainder last) where the
+    // blocked kernels apply, else single sweeps, which take the mask and the
+    // residual slots
+    const bool blocked = jacobi3d_tb_enabled() && !mask && resid_every <= 0 && vec_ok && nz >= 3 &&
+                         ny >= 3 && iters >= 2;
+    const JacobiSchedule sch = jacobi3d_schedule(iters, blocked ? jacobi3d_tb_levels() : 1, false);
+    for (int done = 0; done < iters;) {
+        const int k = sch.depth(done);
+        if (k == 1) {
+            float *r = (resid_every > 0 && (done + 1) % resid_every == 0)
+                           ? resid_out + ((done + 1) / resid_every - 1)
+                           : nullptr;
+            rc = jacobi3d_sweep(a, b, src, mask, nz, ny, nx, 1, nz - 1, h2, dt, pre, r, s);
+        } else {
             rc = jacobi3d_blocked_pass(k, a, b, src, nz, ny, nx, 1, nz - 1, 1, 1, h2, dt, pre, s);
-            if (rc) return rc;
-            if (done == 0 && (rc = launch_fix_faces3d(phi_tmp, phi, nullptr, ny, nx, 0, nz, 0, nz - 1, s)))
-                return rc;
-            done += k;
-            float *t = a;
-            a = b;
-            b = t;
         }
-        timing_end(tk, s, iters);
-        if (a != phi)
-            CFD_CHECK_HIP(hipMemcpyAsync(phi, a, sizeof(float) * plane * nz, hipMemcpyDeviceToDevice, s));
-        return CFD_OK;
-    }
-    for (int it = 0; it < iters; ++it) {
-        float *r = (resid_every > 0 && (it + 1) % resid_every == 0)
-                       ? resid_out + ((it + 1) / resid_every - 1)
-                       : nullptr;
-        if ((rc = jacobi3d_sweep(a, b, src, mask, nz, ny, nx, 1, nz - 1, h2, dt, pre, r, s))) return rc;
-        if (it == 0 && iters > 1 &&
+        if (rc) return rc;
+        // after the first pass the other buffer gets the final faces too (a
+        // single pass: the copy below brings them)
+        if (done == 0 && k < iters &&
             (rc = launch_fix_faces3d(phi_tmp, phi, nullptr, ny, nx, 0, nz, 0, nz - 1, s)))
             return rc;
+        done += k;
         float *t = a;
         a = b;
         b = t;
@@ -742,9 +741,62 @@ int cfd_jacobi3d_zero_f32(const float *div, float *phi, float *phi_tmp, float *r
                             stream);
 }
 
+// The red-black GS solve on the plane range r of an initialised workspace
+// (launch_rbgs_init): cfd_rbgs3d_f32 / _mask2d_f32 (planes 1 .. nz-2 between
+// two Dirichlet planes) and cfd_rbgs3d_zper_f32 (owned planes between
+// periodic ghosts, r.ghost > 0: wrapped after every fused pass, r.ghost
+// deep, or colour, one plane).  mask: (nz, ny, nx), or with mask2d (ny, nx),
+// every plane's.  Only the 2-D mask fuses: the tall-tile passes hold its bits
+// in registers for the whole z-march (jacobi3d_tbr.hip).
+static int rbgs3d_range_solve(float *phi, const float *div, const uint8_t *mask, bool mask2d, const RbgsRange &r,
+                              int ny, int nx, const RbgsConsts &k, int iterations, float *phi_tmp, RbgsWs *w,
+                              int *iters_done, hipStream_t s) {
+    int rc;
+    const int nzo = r.ze - r.zb;  // the planes a periodic wrap copies from
+    const int tk = timing_begin(s);
+    // the 2-D mask fuses when every launch of the solve -- its passes of P
+    // half-sweeps, a shorter last one, the rollbacks (auto tiles) -- has a
+    // masked instantiation; else the colour passes, the same bits
+    const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
+    const uint8_t *m2 = mask2d ? mask : nullptr;
+    const bool m2_ok = !m2 || ((reinterpret_cast<uintptr_t>(m2) & 3u) == 0 &&
+                               rbgs3d_tbr_mask_ok(P, rbgs3d_half_rows(P)) &&
+                               (H % P == 0 || rbgs3d_tbr_mask_ok(H % P, rbgs3d_half_rows(H % P))));
+    if (m2_ok && rbgs3d_fused_ok(phi, phi_tmp, div, mask2d ? nullptr : mask, nx)) {
+        // fused: out-of-place passes of P half-sweeps (colour levels),
+        // ping-pong; the result's buffer and a stop inside a pass are
+        // resolved on the device after the loop.  First the faces no pass
+        // writes, in the other buffer: rows 0 and ny - 1 of every plane,
+        // ghosts included, and the Dirichlet planes in full
+        if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, r.nz, r.fixed_lo ? r.zb - 1 : -1,
+                                     r.fixed_hi ? r.ze : -1, s)))
+            return rc;
+        float *a = phi, *b = phi_tmp;  // the last pass may be shorter
+        for (int h = 0; h < H; h += P) {
+            const int m = H - h >= P ? P : H - h;
+            if ((rc = rbgs3d_half_pass(a, b, div, r.nz, ny, nx, r.zb, r.ze, r.fixed_lo, r.fixed_hi, r.zoff, k, h,
+                                       m, w, s, 0, m2)))
+                return rc;
+            // the ghosts of the buffer just written (a skipped pass: a copy
+            // inside a stale buffer, of the values its ghosts hold already)
+            if (r.ghost && (rc = launch_zper_wrap(b, nzo, ny, nx, r.zb, r.ghost, s))) return rc;
+            float *t = a; a = b; b = t;
+        }
+        timing_end(tk, s, iterations);
+        return rbgs3d_resolve_stop(phi, phi_tmp, div, r, ny, nx, k, P, H, w, iters_done, m2, s);
+    }
+    for (int it = 0; it < iterations; ++it)
+        for (int colour = 0; colour < 2; ++colour) {
+            if ((rc = rbgs3d_colour_pass(colour, phi, div, mask, ny, nx, r.zb, r.ze, r.zoff, k, w, it, s, mask2d)))
+                return rc;
+            if (r.ghost && (rc = launch_zper_wrap(phi, nzo, ny, nx, r.zb, 1, s))) return rc;
+        }
+    timing_end(tk, s, iterations);
+    return launch_rbgs_finish(w, phi, nullptr, (size_t)r.nz * ny * nx, iters_done, s);
+}
+
 // cfd_rbgs3d_f32 (mask (nz, ny, nx)) and cfd_rbgs3d_mask2d_f32 (mask2d: mask
-// (ny, nx), every plane's).  Only the 2-D mask fuses: the tall-tile passes
-// hold its bits in registers for the whole z-march (jacobi3d_tbr.hip).
+// (ny, nx), every plane's)
 static int rbgs3d_solve(float *phi, const float *div, const uint8_t *mask, bool mask2d, int nz, int ny, int nx,
                         double dx, double dy, double dz, float dt, int iterations, double tolerance,
                         float *phi_tmp, void *ws, int *iters_done, void *stream) {
@@ -756,48 +808,8 @@ static int rbgs3d_solve(float *phi, const float *div, const uint8_t *mask, bool 
     int rc = launch_rbgs_init(w, iterations, k.tol, iters_done, s);
     if (rc) return rc;
     if (nz < 3 || ny < 3 || nx < 3 || iterations == 0) return CFD_OK;
-    const size_t n = (size_t)nz * ny * nx;
-    const int tk = timing_begin(s);
-    // the 2-D mask fuses when every launch of the solve -- its passes of P
-    // half-sweeps, a shorter last one, the rollbacks (auto tiles) -- has a
-    // masked instantiation; else the colour passes, the same bits
-    const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
-    const uint8_t *m2 = mask2d ? mask : nullptr;
-    const bool m2_ok = !m2 || ((reinterpret_cast<uintptr_t>(m2) & 3u) == 0 &&
-                               rbgs3d_tbr_mask_ok(P, rbgs3d_half_rows(P)) &&
-                               (H % P == 0 || rbgs3d_tbr_mask_ok(H % P, rbgs3d_half_rows(H % P))));
-    if (m2_ok && rbgs3d_fused_ok(phi, phi_tmp, div, mask2d ? nullptr : mask, nx)) {
-        // fused: out-of-place passes of pp iterations (both colours each),
-        // ping-pong; the result's buffer and a stop inside a pair pass are
-        // resolved on the device after the loop
-        if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, nz, 0, nz - 1, s))) return rc;
-        // passes of P half-sweeps (colour levels), the last one shorter
-        float *a = phi, *b = phi_tmp;
-        for (int h = 0; h < H; h += P) {
-            const int m = H - h >= P ? P : H - h;
-            if ((rc = rbgs3d_half_pass(a, b, div, nz, ny, nx, 1, nz - 1, 1, 1, 0, k, h, m, w, s, 0, m2)))
-                return rc;
-            float *t = a; a = b; b = t;
-        }
-        const int hpp = P;
-        timing_end(tk, s, iterations);
-        if ((rc = launch_rbgs_count(w, iters_done, s))) return rc;
-        // a stop inside a pass: re-run its half-sweeps up to the stop, one
-        // launch per possible count (2c - P j is even when P is); none when
-        // no stop is possible (tolerance <= 0)
-        for (int need = 1; need < hpp && k.tol > 0.f; ++need)
-            if (!(hpp % 2 == 0 && need % 2 == 1) &&
-                (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, nz, ny, nx, 1, nz - 1, 1, 1, 0, k, 0, need, w, hpp,
-                                      H, 0, s, 0, m2)))
-                return rc;
-        return launch_rbgs_copy(w, phi, phi_tmp, n, hpp, s);
-    }
-    for (int it = 0; it < iterations; ++it) {
-        if ((rc = rbgs3d_colour_pass(0, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s, mask2d))) return rc;
-        if ((rc = rbgs3d_colour_pass(1, phi, div, mask, ny, nx, 1, nz - 1, 0, k, w, it, s, mask2d))) return rc;
-    }
-    timing_end(tk, s, iterations);
-    return launch_rbgs_finish(w, phi, nullptr, n, iters_done, s);
+    return rbgs3d_range_solve(phi, div, mask, mask2d, RbgsRange{nz, 1, nz - 1, 1, 1, 0, 0}, ny, nx, k, iterations,
+                              phi_tmp, w, iters_done, s);
 }
 
 int cfd_rbgs3d_f32(float *phi, const float *div, const uint8_t *mask, int nz, int ny, int nx,
@@ -816,8 +828,8 @@ int cfd_rbgs3d_mask2d_f32(float *phi, const float *div, const uint8_t *mask2d, i
 
 int cfd_rbgs3d_zper_ghost(void) { return kZperGhost; }
 
-// cfd_rbgs3d_mask2d_f32 with a periodic z: rbgs3d_solve's two routes on the
-// slab layout (owned planes G .. G + nz - 1 of nz + 2 G, both ends non-fixed,
+// cfd_rbgs3d_mask2d_f32 with a periodic z: rbgs3d_range_solve's two routes on
+// the slab layout (owned planes G .. G + nz - 1 of nz + 2 G, both ends non-fixed,
 // so the fused passes recompute the inner ghost planes' intermediate colours
 // as in cfd_slab_rbgs3d_f32) with the ghost planes wrapped after every pass
 // (fused: G deep) or colour (in place: one plane).
@@ -838,47 +850,12 @@ int cfd_rbgs3d_zper_f32(float *phi, float *div, const uint8_t *mask2d, int nz, i
     if (rc) return rc;
     if (ny < 3 || nx < 3 || iterations == 0) return CFD_OK;
     constexpr int G = kZperGhost;
-    const int nzt = nz + 2 * G, zb = G, ze = G + nz;
-    const int zoff = 0;  // the parity of -G: local plane G is global plane 0
-    const size_t n = (size_t)nzt * ny * nx;
     // the ghosts of the initial guess and, once per solve, of div
     if ((rc = launch_zper_wrap(phi, nz, ny, nx, G, G, s)) || (rc = launch_zper_wrap(div, nz, ny, nx, G, G, s)))
         return rc;
-    const int tk = timing_begin(s);
-    const int P = rbgs3d_half_per_pass(), H = 2 * iterations;
-    const bool m2_ok = !mask2d || ((reinterpret_cast<uintptr_t>(mask2d) & 3u) == 0 &&
-                                   rbgs3d_tbr_mask_ok(P, rbgs3d_half_rows(P)) &&
-                                   (H % P == 0 || rbgs3d_tbr_mask_ok(H % P, rbgs3d_half_rows(H % P))));
-    if (m2_ok && rbgs3d_fused_ok(phi, phi_tmp, div, nullptr, nx)) {
-        // rows 0 and ny - 1 of every plane, ghosts included, in the other buffer
-        if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, 0, nzt, -1, -1, s))) return rc;
-        float *a = phi, *b = phi_tmp;
-        for (int h = 0; h < H; h += P) {
-            const int m = H - h >= P ? P : H - h;
-            if ((rc = rbgs3d_half_pass(a, b, div, nzt, ny, nx, zb, ze, 0, 0, zoff, k, h, m, w, s, 0, mask2d)))
-                return rc;
-            // the ghosts of the buffer just written (a skipped pass: a copy
-            // inside a stale buffer, of the values its ghosts hold already)
-            if ((rc = launch_zper_wrap(b, nz, ny, nx, G, G, s))) return rc;
-            float *t = a; a = b; b = t;
-        }
-        const int hpp = P;
-        timing_end(tk, s, iterations);
-        if ((rc = launch_rbgs_count(w, iters_done, s))) return rc;
-        for (int need = 1; need < hpp && k.tol > 0.f; ++need)
-            if (!(hpp % 2 == 0 && need % 2 == 1) &&
-                (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, nzt, ny, nx, zb, ze, 0, 0, zoff, k, 0, need, w, hpp, H, 0,
-                                      s, 0, mask2d)))
-                return rc;
-        return launch_rbgs_copy(w, phi, phi_tmp, n, hpp, s);
-    }
-    for (int it = 0; it < iterations; ++it)
-        for (int colour = 0; colour < 2; ++colour)
-            if ((rc = rbgs3d_colour_pass(colour, phi, div, mask2d, ny, nx, zb, ze, zoff, k, w, it, s, true)) ||
-                (rc = launch_zper_wrap(phi, nz, ny, nx, G, 1, s)))
-                return rc;
-    timing_end(tk, s, iterations);
-    return launch_rbgs_finish(w, phi, nullptr, n, iters_done, s);
+    // zoff 0, the parity of -G: local plane G is global plane 0
+    return rbgs3d_range_solve(phi, div, mask2d, true, RbgsRange{nz + 2 * G, G, G + nz, 0, 0, 0, G}, ny, nx, k,
+                              iterations, phi_tmp, w, iters_done, s);
 }
 
 int cfd_rbgs3d_pass_f32(const float *in, float *out, const float *div, int nz, int ny, int nx,
@@ -895,9 +872,10 @@ int cfd_rbgs3d_pass_f32(const float *in, float *out, const float *div, int nz, i
                 "rbgs3d_pass: planes [%d,%d) need 1 (fixed) or 2 readable planes on each side (nz %d)",
                 z_begin, z_end, nz);
     const RbgsConsts k = rbgs3d_consts(dx, dy, dz, dt, tolerance);
-    return rbgs3d_fused_pass(in, out, div, nz, ny, nx, z_begin, z_end, fixed_lo, fixed_hi,
-                             z_global_offset, k, iteration, 1, reinterpret_cast<RbgsWs *>(ws),
-                             as_stream(stream));
+    // iteration `iteration`: half-sweeps 2 iteration and 2 iteration + 1
+    return rbgs3d_half_pass(in, out, div, nz, ny, nx, z_begin, z_end, fixed_lo, fixed_hi,
+                            z_global_offset, k, 2 * iteration, 2, reinterpret_cast<RbgsWs *>(ws),
+                            as_stream(stream), 0);
 }
 
 int cfd_rbgs_init(void *ws, int iterations, double tolerance, int *iters_done, void *stream) {

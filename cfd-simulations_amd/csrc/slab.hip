@@ -655,6 +655,72 @@ static int ce_check_attached(SlabComm *c, const float *phi, const float *phi_tmp
     return CFD_OK;
 }
 
+// Whether a pass can run its boundary planes first and overlap their exchange
+// with the interior: a neighbour, and an interior besides 2 G boundary planes
+static bool slab_can_overlap(int overlap, int G, int lo, int hi, int zb, int ze) {
+    return overlap && (lo >= 0 || hi >= 0) && ze - zb >= 2 * G + 1;
+}
+
+// What the passes of one slab solve share: the comm, the main and the exchange
+// stream, the layout (nzl owned planes between G ghost planes per side, of
+// `plane` cells), the neighbours (-1: none), the update range [zb, ze) and
+// whether the plane beyond each end is a Dirichlet plane (else a ghost).
+namespace {
+struct SlabPass {
+    SlabComm *c;
+    hipStream_t s, cs;
+    int nzl, G;
+    size_t plane;
+    int lo, hi, zb, ze, fixed_lo, fixed_hi;
+    bool can_overlap;
+
+    // The ghosts of `a` brought up to date in stream s.  Copy engines: the
+    // copies start behind what s holds so far, and s waits for the
+    // neighbours' planes (and, with maxc and cnt > 0, makes maxc[it0 ..
+    // it0+cnt) the global maxima); else the transport's exchange on s.
+    int update_ghosts(float *a, float *maxc = nullptr, int it0 = 0, int cnt = 0) const {
+        if (!c->ce) return exchange(c, a, nzl, G, plane, lo, hi, s);
+        CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
+        const int rc = exchange_ce(c, a, nzl, G, plane, lo, hi, c->ev_boundary);
+        return rc ? rc : ce_sync(c, s, lo, hi, maxc, it0, cnt);
+    }
+
+    // One pass split for overlap: run(z0, z1) launches planes [z0, z1) on s.
+    // The owned planes a neighbour needs (the G next to it) go first, then
+    // ev_boundary is recorded, then the interior.  The interior is enqueued
+    // before the caller's exchange: the RCCL calls cost the host tens of
+    // microseconds, and the interior does not depend on them (a wait
+    // captures the event as recorded so far).
+    template <typename Run>
+    int split_pass(Run &&run) const {
+        int rc, ib = zb, ie = ze;
+        if (lo >= 0) {
+            if ((rc = run(zb, zb + G))) return rc;
+            ib = zb + G;
+        }
+        if (hi >= 0) {
+            if ((rc = run(ze - G, ze))) return rc;
+            ie = ze - G;
+        }
+        CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
+        return run(ib, ie);
+    }
+};
+}  // namespace
+
+// the argument checks the cfd_slab_* solves share (who: the entry's name)
+static int slab_check_args(const char *who, const SlabComm *c, bool arrays, int nz_local, int ghost, int ny,
+                           int nx, int iters, int zb, int ze, int lo_peer, int hi_peer) {
+    CFD_REQUIRE(c && arrays, "%s: null pointer", who);
+    CFD_REQUIRE(ghost >= 1 && ghost <= 4, "%s: ghost depth must be 1..4", who);
+    CFD_REQUIRE(nz_local >= ghost && ny >= 1 && nx >= 1 && iters >= 0, "%s: bad shape", who);
+    CFD_REQUIRE(zb >= ghost && ze <= nz_local + ghost && zb <= ze,
+                "%s: update range [%d,%d) outside owned planes %d..%d", who, zb, ze, ghost,
+                nz_local + ghost - 1);
+    CFD_REQUIRE(lo_peer < c->nranks && hi_peer < c->nranks, "%s: bad peer", who);
+    return CFD_OK;
+}
+
 }  // namespace cfd
 
 using namespace cfd;
@@ -913,7 +979,6 @@ static int slab_jacobi3d(SlabComm *c, const float *div, float *phi, float *phi_t
                          const uint8_t *mask, int nz_local, int G, int ny, int nx, int lo_peer,
                          int hi_peer, int z_update_begin, int z_update_end, double h, float dt,
                          int iters, int overlap, void *stream, void *comm_stream, bool zero) {
-    const int ghost = G;
     if (iters == 0) {
         if (zero) CFD_CHECK_HIP(hipMemsetAsync(phi, 0, sizeof(float) * (size_t)(nz_local + 2 * G) * ny * nx,
                                                as_stream(stream)));
@@ -921,34 +986,29 @@ static int slab_jacobi3d(SlabComm *c, const float *div, float *phi, float *phi_t
     }
     hipStream_t s = as_stream(stream);
     hipStream_t cs = comm_stream ? as_stream(comm_stream) : s;
-    PartitionScope part(c, overlap && (lo_peer >= 0 || hi_peer >= 0) &&
-                               z_update_end - z_update_begin >= 2 * ghost + 1, s, cs);
+    const int zb = z_update_begin, ze = z_update_end;
+    const bool can_overlap = slab_can_overlap(overlap, G, lo_peer, hi_peer, zb, ze);
+    PartitionScope part(c, can_overlap, s, cs);
     const int nzt = nz_local + 2 * G;
     const size_t plane = (size_t)ny * nx;
+    const SlabPass sl{c, s, cs, nz_local, G, plane, lo_peer, hi_peer, zb, ze, zb > G, ze < nz_local + G, can_overlap};
     const float h2 = (float)(h * h);
     int rc;
     // Dirichlet faces of the owned planes: rows y=0, ny-1, and the global
     // boundary planes (owned planes outside the update range) in full.
     // Ghost planes arrive whole from the neighbours.
-    const int full_lo = z_update_begin > G ? G : -1;
-    const int full_hi = z_update_end < nz_local + G ? nz_local + G - 1 : -1;
-    const int zb = z_update_begin, ze = z_update_end;
+    const int full_lo = sl.fixed_lo ? G : -1;
+    const int full_hi = sl.fixed_hi ? nz_local + G - 1 : -1;
     const bool pre = rhs_ws != nullptr;
     const bool vec_ok = nx % 4 == 0 && aligned16(phi) && aligned16(phi_tmp) && aligned16(div) &&
                         (!pre || aligned16(rhs_ws));
     // k sweeps per pass need k-deep ghosts (and no mask): k = min(G, configured levels)
     const bool tb = G >= 2 && jacobi3d_tb_enabled() && !mask && vec_ok && ny >= 3;
     const int K = tb ? (jacobi3d_tb_levels() < G ? jacobi3d_tb_levels() : G) : 1;
-    // the fused first pass (see above); its depth k1 makes the later passes
+    // the fused first pass (see above); its depth makes the later passes
     // whole passes of K where it can (as in the single-GPU blocked solve)
     const bool first = pre && K >= 2 && jacobi3d_tb_prefetch() == 1 && iters >= 2;
-    int k1 = K;
-    if (first) {
-        const int r = iters % K;
-        k1 = (r == 2 || r == 3) ? r : r == 0 ? K : (K < 3 ? K : 3);
-        if (k1 > iters) k1 = iters;
-    }
-    const int npass = first ? 1 + (iters - k1 + K - 1) / K : (iters + K - 1) / K;
+    const JacobiSchedule sch = jacobi3d_schedule(iters, K, first);
     if (zero && !first) {  // the zero fill, then the general solve
         CFD_CHECK_HIP(hipMemsetAsync(phi, 0, sizeof(float) * plane * nzt, s));
         zero = false;
@@ -977,67 +1037,33 @@ static int slab_jacobi3d(SlabComm *c, const float *div, float *phi, float *phi_t
     if (c->grp && (rc = register_local(c, phi, phi_tmp, nullptr, nz_local, G, plane))) return rc;
     if (c->ce && ((rc = ce_check_attached(c, phi, phi_tmp)) || (rc = ce_begin(c, s, lo_peer, hi_peer)))) return rc;
     // ghosts of the initial guess (a zero start reads none)
-    if (!zero) {
-        if (c->ce) {
-            CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
-            if ((rc = exchange_ce(c, phi, nz_local, G, plane, lo_peer, hi_peer, c->ev_boundary)) ||
-                (rc = ce_sync(c, s, lo_peer, hi_peer, nullptr, 0, 0)))
-                return rc;
-        } else if ((rc = exchange(c, phi, nz_local, G, plane, lo_peer, hi_peer, s))) {
-            return rc;
-        }
-    }
-    const int fixed_lo = zb > G, fixed_hi = ze < nz_local + G;
-    // owned planes a neighbour needs after each pass: the G next to it
-    const bool lo_b = lo_peer >= 0, hi_b = hi_peer >= 0;
-    const bool can_overlap = overlap && (lo_peer >= 0 || hi_peer >= 0) && (ze - zb) >= 2 * G + 1;
+    if (!zero && (rc = sl.update_ghosts(phi))) return rc;
     float *a = phi, *b = phi_tmp;
-    if (zero && npass % 2 == 1) {
+    if (sch.first_into_phi(zero)) {
         a = phi_tmp;
         b = phi;
     }
     const int tk = timing_begin(s);
     int done = 0;
     while (done < iters) {
-        const int k = done == 0 && first ? k1 : iters - done < K ? iters - done : K;
+        const int k = sch.depth(done);
         auto run = [&](int z0, int z1) -> int {
             if (z1 <= z0) return CFD_OK;
             if (done == 0 && first)
                 return jacobi3d_tbr_first_pass(k, b, div, rhs_ws, a, nzt, ny, nx, z0, z1,
-                                               z0 == zb && fixed_lo, z1 == ze && fixed_hi, h2, dt,
+                                               z0 == zb && sl.fixed_lo, z1 == ze && sl.fixed_hi, h2, dt,
                                                jacobi3d_tb_zchunk(), zero, s);
             if (k == 1)
                 return jacobi3d_sweep(a, b, src, mask, nzt, ny, nx, z0, z1, h2, dt, pre, nullptr, s);
-            return jacobi3d_blocked_pass(k, a, b, src, nzt, ny, nx, z0, z1, z0 == zb && fixed_lo,
-                                         z1 == ze && fixed_hi, h2, dt, pre, s);
+            return jacobi3d_blocked_pass(k, a, b, src, nzt, ny, nx, z0, z1, z0 == zb && sl.fixed_lo,
+                                         z1 == ze && sl.fixed_hi, h2, dt, pre, s);
         };
         if (!can_overlap) {
-            if ((rc = run(zb, ze))) return rc;
-            if (c->ce) {
-                CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
-                if ((rc = exchange_ce(c, b, nz_local, G, plane, lo_peer, hi_peer, c->ev_boundary)) ||
-                    (rc = ce_sync(c, s, lo_peer, hi_peer, nullptr, 0, 0)))
-                    return rc;
-            } else if ((rc = exchange(c, b, nz_local, G, plane, lo_peer, hi_peer, s))) {
-                return rc;
-            }
+            if ((rc = run(zb, ze)) || (rc = sl.update_ghosts(b))) return rc;
         } else {
             // boundary planes first, their exchange on the comm stream, the
             // interior meanwhile on the main stream
-            int ib = zb, ie = ze;
-            if (lo_b) {
-                if ((rc = run(zb, zb + G))) return rc;
-                ib = zb + G;
-            }
-            if (hi_b) {
-                if ((rc = run(ze - G, ze))) return rc;
-                ie = ze - G;
-            }
-            // the interior is enqueued before the exchange: the RCCL calls
-            // cost the host tens of microseconds, and the interior does not
-            // depend on them (a wait captures the event as recorded so far)
-            CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
-            if ((rc = run(ib, ie))) return rc;
+            if ((rc = sl.split_pass(run))) return rc;
             if (c->ce) {
                 // copy engines: no CUs, so nothing to reserve; the next pass
                 // waits for the neighbours' planes behind the interior
@@ -1073,17 +1099,11 @@ int cfd_slab_jacobi3d_f32(void *comm, const float *div, float *phi, float *phi_t
                           double h, float dt, int iters, int overlap, void *stream,
                           void *comm_stream) {
     SlabComm *c = reinterpret_cast<SlabComm *>(comm);
-    CFD_REQUIRE(c && div && phi && phi_tmp, "slab_jacobi3d: null pointer");
-    CFD_REQUIRE(ghost >= 1 && ghost <= 4, "slab_jacobi3d: ghost depth must be 1..4");
-    CFD_REQUIRE(nz_local >= ghost && ny >= 1 && nx >= 1 && iters >= 0, "slab_jacobi3d: bad shape");
-    const int G = ghost;
-    CFD_REQUIRE(z_update_begin >= G && z_update_end <= nz_local + G &&
-                    z_update_begin <= z_update_end,
-                "slab_jacobi3d: update range [%d,%d) outside owned planes %d..%d", z_update_begin,
-                z_update_end, G, nz_local + G - 1);
-    CFD_REQUIRE(lo_peer < c->nranks && hi_peer < c->nranks, "slab_jacobi3d: bad peer");
+    if (int rc = slab_check_args("slab_jacobi3d", c, div && phi && phi_tmp, nz_local, ghost, ny, nx, iters,
+                                 z_update_begin, z_update_end, lo_peer, hi_peer))
+        return rc;
     if (iters == 0) return CFD_OK;
-    return slab_jacobi3d(c, div, phi, phi_tmp, rhs_ws, mask, nz_local, G, ny, nx, lo_peer, hi_peer,
+    return slab_jacobi3d(c, div, phi, phi_tmp, rhs_ws, mask, nz_local, ghost, ny, nx, lo_peer, hi_peer,
                          z_update_begin, z_update_end, h, dt, iters, overlap, stream, comm_stream, false);
 }
 
@@ -1092,14 +1112,9 @@ int cfd_slab_jacobi3d_zero_f32(void *comm, const float *div, float *phi, float *
                                int hi_peer, int z_update_begin, int z_update_end, double h, float dt,
                                int iters, int overlap, void *stream, void *comm_stream) {
     SlabComm *c = reinterpret_cast<SlabComm *>(comm);
-    CFD_REQUIRE(c && div && phi && phi_tmp, "slab_jacobi3d_zero: null pointer");
-    CFD_REQUIRE(ghost >= 1 && ghost <= 4, "slab_jacobi3d_zero: ghost depth must be 1..4");
-    CFD_REQUIRE(nz_local >= ghost && ny >= 1 && nx >= 1 && iters >= 0, "slab_jacobi3d_zero: bad shape");
-    CFD_REQUIRE(z_update_begin >= ghost && z_update_end <= nz_local + ghost &&
-                    z_update_begin <= z_update_end,
-                "slab_jacobi3d_zero: update range [%d,%d) outside owned planes %d..%d", z_update_begin,
-                z_update_end, ghost, nz_local + ghost - 1);
-    CFD_REQUIRE(lo_peer < c->nranks && hi_peer < c->nranks, "slab_jacobi3d_zero: bad peer");
+    if (int rc = slab_check_args("slab_jacobi3d_zero", c, div && phi && phi_tmp, nz_local, ghost, ny, nx, iters,
+                                 z_update_begin, z_update_end, lo_peer, hi_peer))
+        return rc;
     return slab_jacobi3d(c, div, phi, phi_tmp, rhs_ws, nullptr, nz_local, ghost, ny, nx, lo_peer, hi_peer,
                          z_update_begin, z_update_end, h, dt, iters, overlap, stream, comm_stream, true);
 }
@@ -1121,27 +1136,21 @@ int cfd_slab_rbgs3d_f32(void *comm, const float *div, float *phi, float *phi_tmp
                         double tolerance, void *ws, int *iters_done, int overlap, void *stream,
                         void *comm_stream) {
     SlabComm *c = reinterpret_cast<SlabComm *>(comm);
-    CFD_REQUIRE(c && div && phi && ws, "slab_rbgs3d: null pointer");
-    CFD_REQUIRE(ghost >= 1 && ghost <= 4, "slab_rbgs3d: ghost depth must be 1..4");
-    CFD_REQUIRE(nz_local >= ghost && ny >= 1 && nx >= 1 && iterations >= 0, "slab_rbgs3d: bad shape");
-    const int G = ghost;
-    CFD_REQUIRE(z_update_begin >= G && z_update_end <= nz_local + G &&
-                    z_update_begin <= z_update_end,
-                "slab_rbgs3d: update range [%d,%d) outside owned planes %d..%d", z_update_begin,
-                z_update_end, G, nz_local + G - 1);
-    CFD_REQUIRE(lo_peer < c->nranks && hi_peer < c->nranks, "slab_rbgs3d: bad peer");
+    int rc = slab_check_args("slab_rbgs3d", c, div && phi && ws, nz_local, ghost, ny, nx, iterations,
+                             z_update_begin, z_update_end, lo_peer, hi_peer);
+    if (rc) return rc;
+    const int G = ghost, zb = z_update_begin, ze = z_update_end, zoff = z_global_offset;
     hipStream_t s = as_stream(stream);
     hipStream_t cs = comm_stream ? as_stream(comm_stream) : s;
-    PartitionScope part(c, overlap && (lo_peer >= 0 || hi_peer >= 0) &&
-                               z_update_end - z_update_begin >= 2 * ghost + 1, s, cs);
+    const bool can_overlap = slab_can_overlap(overlap, G, lo_peer, hi_peer, zb, ze);
+    PartitionScope part(c, can_overlap, s, cs);
     RbgsWs *w = reinterpret_cast<RbgsWs *>(ws);
     const RbgsConsts k = rbgs3d_consts(dx, dy, dz, dt, tolerance);
-    int rc = launch_rbgs_init(w, iterations, k.tol, iters_done, s);
+    rc = launch_rbgs_init(w, iterations, k.tol, iters_done, s);
     if (rc || iterations == 0 || ny < 3 || nx < 3) return rc;
     const int nzt = nz_local + 2 * G;
     const size_t plane = (size_t)ny * nx;
-    const int zb = z_update_begin, ze = z_update_end, zoff = z_global_offset;
-    const int fixed_lo = zb > G, fixed_hi = ze < nz_local + G;
+    const SlabPass sl{c, s, cs, nz_local, G, plane, lo_peer, hi_peer, zb, ze, zb > G, ze < nz_local + G, can_overlap};
     // a one-rank comm peered with itself (the per-rank rehearsal) reduces too
     const bool self_peered = !c->grp && (lo_peer == c->rank || hi_peer == c->rank);
     const bool reduce = (c->nranks > 1 || self_peered) && k.tol > 0.0f;
@@ -1152,49 +1161,34 @@ int cfd_slab_rbgs3d_f32(void *comm, const float *div, float *phi, float *phi_tmp
         return CFD_OK;
     };
     if (c->grp && (rc = register_local(c, phi, phi_tmp, w, nz_local, G, plane))) return rc;
-    // copy engines: the exchange of `a` and the next pass's wait for it (with
-    // the global maxima of iterations it .. it+cnt-1 when cnt > 0)
-    auto ce_step = [&](float *a, int it, int cnt) -> int {
-        int r;
-        CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
-        if ((r = exchange_ce(c, a, nz_local, G, plane, lo_peer, hi_peer, c->ev_boundary))) return r;
-        return ce_sync(c, s, lo_peer, hi_peer, reduce ? w->maxc : nullptr, it, cnt);
-    };
+    // copy engines: their sync behind an exchange also combines the maxima of
+    // the iterations it is given, so no allreduce follows it
+    float *const ce_maxc = reduce ? w->maxc : nullptr;
     if (c->ce && ((rc = ce_check_attached(c, phi, phi_tmp)) || (rc = ce_begin(c, s, lo_peer, hi_peer)))) return rc;
     // ghosts of the initial guess
-    if (c->ce) {
-        if ((rc = ce_step(phi, 0, 0))) return rc;
-    } else if ((rc = exchange(c, phi, nz_local, G, plane, lo_peer, hi_peer, s))) {
-        return rc;
-    }
+    if ((rc = sl.update_ghosts(phi, ce_maxc, 0, 0))) return rc;
     const int tk = timing_begin(s);
     const bool fused = G >= 2 && rbgs3d_fused_ok(phi, phi_tmp, div, mask, nx);
     if (!fused) {
         for (int it = 0; it < iterations; ++it) {
-            for (int colour = 0; colour < 2; ++colour) {
-                if ((rc = rbgs3d_colour_pass(colour, phi, div, mask, ny, nx, zb, ze, zoff, k, w, it, s)))
+            for (int colour = 0; colour < 2; ++colour)  // (copy engines: maxima after colour 1)
+                if ((rc = rbgs3d_colour_pass(colour, phi, div, mask, ny, nx, zb, ze, zoff, k, w, it, s)) ||
+                    (rc = sl.update_ghosts(phi, ce_maxc, it, colour)))
                     return rc;
-                if (c->ce) {
-                    if ((rc = ce_step(phi, it, colour))) return rc;  // maxima after colour 1
-                } else if ((rc = exchange(c, phi, nz_local, G, plane, lo_peer, hi_peer, s))) {
-                    return rc;
-                }
-            }
             if (!c->ce && (rc = allreduce(it, 1, s))) return rc;
         }
         if (c->ce && (rc = ce_join(c, s))) return rc;
         timing_end(tk, s, iterations);
         return launch_rbgs_finish(w, phi, nullptr, plane * nzt, iters_done, s);
     }
-    // pp iterations per pass need 2*pp-deep ghosts (the pass recomputes the
-    // inner ghost planes' intermediate colours)
-    const int pp = rbgs3d_iters_per_pass() == 2 && G >= 4 ? 2 : 1;
+    // passes of P half-sweeps (colour levels), whole iterations: P-deep ghosts
+    // (the pass recomputes the inner ghost planes' intermediate colours)
+    const int P = rbgs3d_iters_per_pass() == 2 && G >= 4 ? 4 : 2, H = 2 * iterations;
     // owned faces the passes never write, in both buffers
-    const int full_lo = fixed_lo ? G : -1;
-    const int full_hi = fixed_hi ? nz_local + G - 1 : -1;
+    const int full_lo = sl.fixed_lo ? G : -1;
+    const int full_hi = sl.fixed_hi ? nz_local + G - 1 : -1;
     if ((rc = launch_fix_faces3d(phi, phi_tmp, nullptr, ny, nx, G, nz_local + G, full_lo, full_hi, s)))
         return rc;
-    const bool can_overlap = overlap && (lo_peer >= 0 || hi_peer >= 0) && (ze - zb) >= 2 * G + 1;
     // Lagged stop test (overlapped, one iteration per pass): pass j tests
     // maxc[j-2] and maxc[j-3] instead of maxc[j-1] and maxc[j-2], so the
     // allreduce of iteration j-1 runs beside pass j's boundary launches
@@ -1202,63 +1196,45 @@ int cfd_slab_rbgs3d_f32(void *comm, const float *div, float *phi, float *phi_tmp
     // wasted pass n+1; it writes the buffer of iteration n-1, so iteration n's
     // result is intact, and maxc of a skipped pass stays 0 (< tol), which keeps
     // every later pass skipped.  rbgs_count / rbgs_copy are unchanged.
-    const int lag = can_overlap && reduce && pp == 1 && !c->ce ? 1 : 0;
+    const int lag = can_overlap && reduce && P == 2 && !c->ce ? 1 : 0;
     float *a = phi, *b = phi_tmp;
-    for (int it = 0; it < iterations;) {
-        const int m = iterations - it >= pp ? pp : 1;
+    for (int h = 0; h < H;) {
+        const int m = H - h >= P ? P : 2;
+        const int it = h / 2, ni = m / 2;  // the pass's iterations: it .. it + ni - 1
         auto run = [&](int z0, int z1) -> int {
             if (z1 <= z0) return CFD_OK;
-            return rbgs3d_fused_pass(a, b, div, nzt, ny, nx, z0, z1, z0 == zb && fixed_lo,
-                                     z1 == ze && fixed_hi, zoff, k, it, m, w, s, lag);
+            return rbgs3d_half_pass(a, b, div, nzt, ny, nx, z0, z1, z0 == zb && sl.fixed_lo,
+                                    z1 == ze && sl.fixed_hi, zoff, k, h, m, w, s, lag);
         };
         if (!can_overlap) {
-            if ((rc = run(zb, ze))) return rc;
-            if (c->ce) {
-                if ((rc = ce_step(b, it, m))) return rc;
-            } else if ((rc = exchange(c, b, nz_local, G, plane, lo_peer, hi_peer, s)) ||
-                       (rc = allreduce(it, m, s))) {
+            if ((rc = run(zb, ze)) || (rc = sl.update_ghosts(b, ce_maxc, it, ni)) ||
+                (!c->ce && (rc = allreduce(it, ni, s))))
                 return rc;
-            }
         } else {
-            int ib = zb, ie = ze;
-            if (lo_peer >= 0) {
-                if ((rc = run(zb, zb + G))) return rc;
-                ib = zb + G;
-            }
-            if (hi_peer >= 0) {
-                if ((rc = run(ze - G, ze))) return rc;
-                ie = ze - G;
-            }
-            // interior enqueued before the exchange (see the Jacobi driver)
-            CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
-            if ((rc = run(ib, ie))) return rc;
+            if ((rc = sl.split_pass(run))) return rc;
             if (c->ce) {
                 // copies started after the boundary planes; the sync behind
                 // the interior waits for the ghosts and combines the maxima
                 if ((rc = exchange_ce(c, b, nz_local, G, plane, lo_peer, hi_peer, c->ev_boundary)) ||
-                    (rc = ce_sync(c, s, lo_peer, hi_peer, reduce ? w->maxc : nullptr, it, m)))
+                    (rc = ce_sync(c, s, lo_peer, hi_peer, ce_maxc, it, ni)))
                     return rc;
-                it += m;
-                float *t = a;
-                a = b;
-                b = t;
-                continue;
-            }
-            CFD_CHECK_HIP(hipStreamWaitEvent(cs, c->ev_boundary, 0));
-            if ((rc = exchange(c, b, nz_local, G, plane, lo_peer, hi_peer, cs))) return rc;
-            // lagged: the next pass waits for the exchange only (and, through
-            // the in-order exchange stream, for the previous allreduce)
-            if (lag) CFD_CHECK_HIP(hipEventRecord(c->ev_comm, cs));
-            if (reduce) {
-                // the global max needs the interior's contribution too
-                CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
+            } else {
                 CFD_CHECK_HIP(hipStreamWaitEvent(cs, c->ev_boundary, 0));
-                if ((rc = allreduce(it, m, cs))) return rc;
+                if ((rc = exchange(c, b, nz_local, G, plane, lo_peer, hi_peer, cs))) return rc;
+                // lagged: the next pass waits for the exchange only (and, through
+                // the in-order exchange stream, for the previous allreduce)
+                if (lag) CFD_CHECK_HIP(hipEventRecord(c->ev_comm, cs));
+                if (reduce) {
+                    // the global max needs the interior's contribution too
+                    CFD_CHECK_HIP(hipEventRecord(c->ev_boundary, s));
+                    CFD_CHECK_HIP(hipStreamWaitEvent(cs, c->ev_boundary, 0));
+                    if ((rc = allreduce(it, ni, cs))) return rc;
+                }
+                if (!lag) CFD_CHECK_HIP(hipEventRecord(c->ev_comm, cs));
+                CFD_CHECK_HIP(hipStreamWaitEvent(s, c->ev_comm, 0));
             }
-            if (!lag) CFD_CHECK_HIP(hipEventRecord(c->ev_comm, cs));
-            CFD_CHECK_HIP(hipStreamWaitEvent(s, c->ev_comm, 0));
         }
-        it += m;
+        h += m;
         float *t = a;
         a = b;
         b = t;
@@ -1271,12 +1247,8 @@ int cfd_slab_rbgs3d_f32(void *comm, const float *div, float *phi, float *phi_tmp
     timing_end(tk, s, iterations);
     // count (same on every rank: the maxima are global), re-run a pair
     // pass's first iteration if the stop fell inside it, pick the buffer
-    if ((rc = launch_rbgs_count(w, iters_done, s))) return rc;
-    if (pp == 2 &&
-        (rc = rbgs3d_tbr_pass(phi, phi_tmp, div, nzt, ny, nx, zb, ze, fixed_lo, fixed_hi, zoff, k, 0, 2,
-                              w, 4, 2 * iterations, 0, s)))
-        return rc;
-    return launch_rbgs_copy(w, phi, phi_tmp, plane * nzt, 2 * pp, s);
+    const RbgsRange range{nzt, zb, ze, sl.fixed_lo, sl.fixed_hi, zoff, 0};
+    return rbgs3d_resolve_stop(phi, phi_tmp, div, range, ny, nx, k, P, H, w, iters_done, nullptr, s);
 }
 
 }  // extern "C"

@@ -196,7 +196,8 @@ def test_jacobi3d_temporal_blocking_bitexact(shape, iters, rows, zchunk, prefetc
 @pytest.mark.parametrize("levels,rows", [(3, 16), (3, 17), (3, 18), (3, 0), (4, 14), (4, 15), (4, 16),
                                          (2, 0)])
 @pytest.mark.parametrize("shape,iters", [((9, 10, 12), 7), ((21, 30, 264), 8), ((40, 31, 520), 12),
-                                         ((5, 4, 8), 4), ((13, 40, 16), 9), ((12, 47, 264), 8)])
+                                         ((5, 4, 8), 4), ((13, 40, 16), 9), ((12, 47, 264), 8),
+                                         ((7, 9, 16), 6)])
 @pytest.mark.parametrize("zchunk", [0, 1, 5])
 @pytest.mark.parametrize("prefetch", [1, 2])
 def test_jacobi3d_k_levels_bitexact(shape, iters, levels, rows, zchunk, prefetch):
@@ -872,6 +873,34 @@ def test_slab_jacobi_local_group_multirank(R, ghost, overlap, iters):
         return sj
 
     sols = _run_local_group(R, make, lambda sj: sj.solve(iters, overlap=overlap))
+    got = np.concatenate([host(sj.owned()) for sj in sols])
+    assert np.array_equal(got, ref)
+
+
+@pytest.mark.parametrize("ghost", [1, 2, 4])
+@pytest.mark.parametrize("overlap", [False, True])
+@pytest.mark.parametrize("rhs", [False, True], ids=["norhs", "rhs"])
+@pytest.mark.parametrize("iters", [5, 7, 8])
+def test_slab_jacobi_local_group_from_a_guess(ghost, overlap, rhs, iters):
+    """cfd_slab_jacobi3d_f32 from a non-zero guess (its ghosts exchanged first,
+    the faces copied back after the first pass), with and without the RHS
+    workspace's fused first pass: 2 ranks of 6 owned planes, pass schedules
+    with iters mod K = 0..3 -- bit-identical to the oracle."""
+    R, nz, ny, nx = 2, 12, 9, 16
+    rng = np.random.default_rng(50)
+    div = rng.standard_normal((nz, ny, nx)).astype(np.float32)
+    phi0 = rng.standard_normal((nz, ny, nx)).astype(np.float32)
+    ref = oracle.jacobi3d(div, phi0, h=0.05, dt=np.float32(1e-3), iters=iters)
+
+    def make(r, comm):
+        plan = S.SlabPlan(nz, R, r, ghost=ghost)
+        sj = S.SlabJacobi3D(plan, ny, nx, 0.05, np.float32(1e-3), comm, rhs_workspace=rhs)
+        sj.div.copy_(dev(plan.scatter(div)))
+        own = plan.owned()
+        sj.phi[own].copy_(dev(phi0[plan.z_lo:plan.z_hi]))  # ghosts left zero: the driver fetches them
+        return sj
+
+    sols = _run_local_group(R, make, lambda sj: sj.solve(iters, overlap=overlap, zero_phi=False))
     got = np.concatenate([host(sj.owned()) for sj in sols])
     assert np.array_equal(got, ref)
 
