@@ -275,6 +275,8 @@ STEP_CASES = {
     "rbgs-upwind": dict(CUBE, y_max=3.0, use_supg=False, cylinder_center=(1.5, 1.5)),
     "rbgs-les": dict(CUBE, z_max=1.0, use_les=True),
     "jacobi-from-1000": dict(CUBE, use_fast_pressure=False),
+    # initial_steps = 7, started at step 3: both forcing calls run at 3/7, 4/7, 5/7 (no power of two)
+    "rbgs-ramp-from-3": dict(CUBE, y_max=3.0, z_max=1.0, cylinder_center=(1.5, 1.5), initial_steps=7),
 }
 FIELDS = ("u", "v", "w", "phi", "u_star", "v_star", "w_star", "div_u_star")
 
@@ -304,6 +306,9 @@ def test_cylinder3d_steps_bitexact(case):
     assert 1 < i0 < i1 < c.ny - 1 and 1 < j0 < j1 < c.nx - 2   # a box inside the plane
     if case.endswith("1000"):
         g.step = o.step = 1000   # the adaptive dt's read runs, the forcing is at full strength
+    if case.endswith("from-3"):
+        g.step = o.step = 3      # the ramp min(1, step / 7) at 3/7, 4/7, 5/7
+        assert c.initial_steps == 7
     first = g.step
     for k in range(first, first + 3):
         compare_step(g, o, k)

@@ -300,6 +300,8 @@ STEP_CASES = {
     "rbgs-les": dict(CUBE, z_max=1.0, use_les=True, **SCALAR),
     "rbgs-from-1000": dict(CUBE, z_max=1.0, **SCALAR),
     "periodic": dict(CUBE, z_max=1.0, spanwise_bc="periodic", spanwise_perturbation=0.05, **SCALAR),
+    # initial_steps = 7, started at step 3: the forcing and the heating run at 3/7, 4/7, 5/7
+    "rbgs-ramp-from-3": dict(CUBE, y_max=3.0, z_max=1.0, cylinder_center=(1.5, 1.5), initial_steps=7, **SCALAR),
 }
 
 
@@ -316,6 +318,9 @@ def test_cylinder3d_scalar_steps(case):
     assert np.array_equal(host(g.T), o.T) and (o.T == F(0.25)).all()
     if case.endswith("1000"):
         g.step = o.step = plain.step = 1000   # full forcing strength, adaptive dt
+    if case.endswith("from-3"):
+        g.step = o.step = plain.step = 3      # the ramp min(1, step / 7) at 3/7, 4/7, 5/7
+        assert c.initial_steps == 7
     first = g.step
     for k in range(first, first + 3):
         assert g.time_step() == o.time_step() == plain.time_step(), k
