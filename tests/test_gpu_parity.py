@@ -797,8 +797,9 @@ def test_slab_copy_engine_multiprocess(world, landing):
     its own process on this GPU (torch.distributed.run, gloo for the IPC
     handle blobs), mapping each other's buffers and flag blocks.  Jacobi
     (ghost 1 and 3, zero and nonzero start, overlap on / off) and red-black GS
-    (one and two iterations per pass, fixed count and early stop through the
-    gathered global maxima): the gathered owned planes equal the single-domain
+    (in place with ghost 1 -- the maxima gathered behind colour 1 -- and fused
+    with one and two iterations per pass, fixed count and early stop through
+    the gathered global maxima): the gathered owned planes equal the single-domain
     oracle bit for bit (scripts/multirank_check.py).  landing: every rank takes
     its ghosts through its landing buffer (CFD_CE_LANDING=1, the path of pairs
     of 2 GiB or more, which IPC cannot map: the 1024^3 grid at two ranks)."""
